@@ -2,6 +2,7 @@
 """Benchmark: 1024x1024 images/sec through the quantized SAM image encoder.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode w4a16|w4a8|w8a8]
+                    [--full] [--dump-outputs DIR]
 
 Default (the headline, BASELINE config 3/4): ``--mode w4a16`` = ViT-H GPTQ int4 weights x fp16
 activations.  ``--mode w4a8`` (config 5): ViT-H int4 weights x int8 activations on the int8 MFMA,
@@ -20,11 +21,16 @@ sharded contiguously over the ranks (``samq.dist.shard``); per-GPU work is fixed
 scaling): 4 images per GPU at N=1 (BASELINE config 3), 8 per GPU at N>1 (config 4 at N=8 =
 global batch 64).
 
-Besides the throughput line, it reports for the dominant kernel (all W4A16 GEMM launches of one
-forward) its roofline fraction measured INSIDE the timed configuration (HIP events captured into
-the same HIP graph as external event nodes, on each lane's stream; see ``step_profile``), the
-isolated-launch figure next to it, and the CPU baseline: the oracle restatement of the
-reference's fp32 CPU fake-quant path (median of 3 one-image runs after one warm-up, rank 0, N=1).
+A plain run sets up, warms up, times the steps and prints the throughput line; its roofline stanza
+quotes the committed in-step profile of this build when there is one.  ``--dump-outputs DIR``
+also writes rank 0's encoder output of the last timed step to ``DIR/image_embeddings.npy``
+(weights and images are seeded: the same arguments give the same inputs in every run).
+
+``--full`` adds, after the timed steps: the isolated-launch roofline figure of the dominant kernel
+(all projection GEMM launches of one forward) next to the in-step one, the CPU baseline (the
+oracle restatement of the reference's fp32 CPU fake-quant path, median of 3 one-image runs after
+one warm-up, rank 0, N=1), parity + mask IoU of the timed graph's own output against the oracle,
+and, in a 1-GPU W4A16 run, the W4A8 (config 5) and W8A8 (config 2) sub-records.
 
 ``--dry-run --backend gloo`` exercises the launcher / sharding / weight broadcast on the CPU
 (tiny model, no GPU) for the multi-process tests.
@@ -585,6 +591,29 @@ def local_images(start: int, stop: int, dev, dtype, size: int = 1024) -> torch.T
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, arrays: dict) -> None:
+    """``--dump-outputs``: write what the timed path returned in its last timed step as
+    ``<directory>/<name>.npy`` (float32; float64 stays float64), at most 64 MB in all.  An array
+    over its share of the limit is stored as a fixed sample: the flat elements at sorted indices
+    drawn from seed 0, so two builds run with the same arguments store the same elements."""
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        keep = (share - 1024) // t.element_size()   # 1 KiB left for the .npy header
+        if t.numel() > keep:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(t.numel(), (keep,), generator=g).sort().values
+            t = t.flatten()[idx.to(t.device)]
+        np.save(d / f"{name}.npy", t.cpu().numpy())
+
+
 def dry_run(args, rank: int, world: int) -> None:
     """CPU rehearsal of the multi-rank path (gloo): shard the seeded global batch, broadcast a
     tiny quantised encoder from rank 0, gather per-rank shard / checksum records on rank 0."""
@@ -711,6 +740,8 @@ def run_mode(mode: str, args, rank: int, world: int, dev, batch: int, lanes: int
     else:
         t_bc_max, t_init_max = t_bc, t_init
     out0 = holder["out"][0:1].float().clone() if stop > start else None
+    if headline and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image_embeddings": holder["out"]})
 
     rows = stop - start
     per_launch_imgs = rows // lanes
@@ -806,9 +837,17 @@ def main():
     ap.add_argument("--lanes", type=int, default=0,
                     help="image groups run as concurrent kernel chains on separate HIP streams "
                          "(0 = 2 when the per-GPU batch is even, else 1; W8A8 runs one chain)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: the isolated GEMM "
+                         "roofline passes, the CPU baseline, parity + mask IoU of the timed output against the "
+                         "oracle, and (1-GPU W4A16) the W4A8 / W8A8 sub-records; without it a run sets up, warms "
+                         "up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write rank 0's encoder output of the last timed step to "
+                         "DIR/image_embeddings.npy (float32; a seeded sample above 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-modes", action="store_true",
-                    help="headline only: skip the W4A8 (config 5) / W8A8 (config 2) sub-records that a default "
+                    help="headline only: skip the W4A8 (config 5) / W8A8 (config 2) sub-records that a --full "
                          "1-GPU W4A16 run appends")
     ap.add_argument("--lane-stagger", type=int, default=None,
                     help="W4A16 lanes: lane i+1 waits for lane i's launch k (7 per block; -1 = none; default: the engine's 1)")
@@ -820,6 +859,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the multi-rank path (no GPU)")
     argv = sys.argv[1:]
     args = ap.parse_args(argv)
+    if not args.full:   # a plain run: the headline alone (the --no-* switches trim a --full run)
+        args.no_cpu_baseline = args.no_isolated = args.no_modes = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, argv))

@@ -277,3 +277,25 @@ def test_bench_int8_parity_gate_cpu():
     rec = bench.parity_report("w8a8", flip, ref, {"fp64": ref.clone()})
     assert rec["pass"] is False
     assert bench.parity_report("w4a8", near.clone(), ref)["pass"] is True   # no points: absolute 0.35
+
+
+def test_bench_dump_outputs_cpu(tmp_path, monkeypatch):
+    """bench.dump_outputs (``--dump-outputs``): an array within the size limit is stored whole as
+    float32; one above it as a fixed seeded sample -- the same flat elements in every run, in index
+    order, float64 kept as float64 -- and the files stay within the limit."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn((2, 3, 16, 16), generator=g)
+    bench.dump_outputs(tmp_path / "a", {"image_embeddings": x.half()})
+    got = np.load(tmp_path / "a" / "image_embeddings.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 16, 16)
+    np.testing.assert_array_equal(got, x.half().float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    y = torch.randn(5000, generator=g, dtype=torch.float64)
+    bench.dump_outputs(tmp_path / "b", {"y": y})
+    bench.dump_outputs(tmp_path / "c", {"y": y})
+    s1, s2 = np.load(tmp_path / "b" / "y.npy"), np.load(tmp_path / "c" / "y.npy")
+    assert s1.dtype == np.float64 and 0 < s1.size < y.numel() and np.array_equal(s1, s2)
+    assert (tmp_path / "b" / "y.npy").stat().st_size <= 4096
+    assert np.isin(s1, y.numpy()).all()

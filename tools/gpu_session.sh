@@ -66,19 +66,19 @@ for step in "$@"; do
     decoder)  run decoder 600 $PYT -q tests/test_sam_decoder.py ;;
     k=*)      run k_$(echo "$arg" | tr -c 'a-zA-Z0-9' '_') 900 $PYT -q tests -k "$arg" ;;
     smoke)    run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)    run bench 600 python bench.py --steps 20 --warmup 5 ;;
-    bench48)  run bench48 600 python bench.py --mode w4a8 --steps 10 --warmup 3 ;;
-    bench88)  run bench88 600 python bench.py --mode w8a8 --steps 20 --warmup 5 ;;
-    benchg)   run benchg 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --groupsize 128 ;;
-    benchq)   run benchq 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    b48q)     run b48q 400 python bench.py --mode w4a8 --steps 10 --warmup 3 --no-cpu-baseline ;;
-    b88q)     run b88q 400 python bench.py --mode w8a8 --steps 20 --warmup 5 --no-cpu-baseline ;;
+    bench)    run bench 600 python bench.py --full --steps 20 --warmup 5 ;;
+    bench48)  run bench48 600 python bench.py --full --mode w4a8 --steps 10 --warmup 3 ;;
+    bench88)  run bench88 600 python bench.py --full --mode w8a8 --steps 20 --warmup 5 ;;
+    benchg)   run benchg 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --groupsize 128 ;;
+    benchq)   run benchq 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ;;
+    b48q)     run b48q 400 python bench.py --full --mode w4a8 --steps 10 --warmup 3 --no-cpu-baseline ;;
+    b88q)     run b88q 400 python bench.py --full --mode w8a8 --steps 20 --warmup 5 --no-cpu-baseline ;;
     instep)   run instep 500 bash tools/instep_profile.sh w4a16 ;;
     instep48) run instep48 500 bash tools/instep_profile.sh w4a8 ;;
     instep88) run instep88 500 bash tools/instep_profile.sh w8a8 ;;
     instepg)  run instepg 500 bash tools/instep_profile.sh w4a16 --groupsize 128 ;;
     instep8)  run instep8 500 bash tools/instep_profile.sh w4a16 --batch 8 ;;
-    rehearse) run rehearse 600 python bench.py --gpus 2 --backend gloo --steps 5 --warmup 2 ;;
+    rehearse) run rehearse 600 python bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 2 ;;
     pmc)      run pmc 900 bash tools/pmc_all.sh ;;
     publish=*) H=$(python3 -c "import bench; print(bench.source_hash())")
               cp gpurun_out/instep_*_"$H".json gpurun_out/instep_*_"$H"_wholerun_stats.csv profiles/ || exit 1
@@ -87,7 +87,7 @@ for step in "$@"; do
 import json, sys
 m, r, h, rnd = sys.argv[1:]
 src = (f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/pmc_all.sh via tools/gpu_session.sh) "
-       f"over `python3 bench.py --mode {m} --steps 2 --warmup 1 --no-cpu-baseline --no-graph` (GEMM M = {r} per "
+       f"over `python3 bench.py --full --mode {m} --steps 2 --warmup 1 --no-cpu-baseline --no-graph` (GEMM M = {r} per "
        f"launch) on MI355X, build {h}; hbm = 2*FETCH_SIZE + WRITE_SIZE per dispatch (MI355X_MICROARCH.md HBM "
        f"section: gfx950 FETCH_SIZE counts half of 16-B/lane streaming reads; Infinity-Cache hits included)")
 out = {"source": src, "kernels": json.load(open(f"gpurun_out/pmc_{m}.json"))}

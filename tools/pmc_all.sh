@@ -10,7 +10,7 @@ for mode in w4a16 w4a8 w8a8; do
     d=gpurun_out/pmc_${mode}_$(echo $c | tr A-Z a-z | cut -d_ -f1)
     rm -rf "$d"
     timeout -s KILL 300 rocprofv3 --pmc $c --output-format csv -d "$d" -o run -- \
-      python3 bench.py --mode $mode --steps 2 --warmup 1 --no-cpu-baseline --no-graph > "$d.log" 2>&1 \
+      python3 bench.py --full --mode $mode --steps 2 --warmup 1 --no-cpu-baseline --no-graph > "$d.log" 2>&1 \
       || { echo "pmc pass $mode $c failed rc=$?"; tail -20 "$d.log"; exit 1; }
   done
   python3 tools/pmc_summary.py gpurun_out/pmc_${mode}_fetch gpurun_out/pmc_${mode}_write > gpurun_out/pmc_$mode.json || exit 1

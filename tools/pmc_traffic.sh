@@ -4,7 +4,7 @@
 # usage: tools/pmc_traffic.sh [bench args...]   -> gpurun_out/pmc_fetch/, gpurun_out/pmc_write/
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
-ARGS=${*:-"--steps 2 --warmup 1 --no-cpu-baseline --no-graph"}
+ARGS=${*:-"--full --steps 2 --warmup 1 --no-cpu-baseline --no-graph"}
 for c in FETCH_SIZE WRITE_SIZE; do
   d=gpurun_out/pmc_$(echo $c | tr A-Z a-z | cut -d_ -f1)
   timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $d -o run -- python3 bench.py $ARGS \
