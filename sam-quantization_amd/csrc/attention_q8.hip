@@ -13,7 +13,8 @@
 // Arithmetic (all exact or fp32, SURVEY.md §8c Oracle F):
 //   * q.k on v_mfma_i32_16x16x64_i8: exact int32; value = int * (s_qkv * scale * s_qkv);
 //   * rel_h / rel_w: fp32 dot products of the fake-quant q (code * s_qkv) with the f32 tables;
-//   * the two score quantisers use a true division and round-half-to-even (uniform.py:31-36);
+//   * the two score quantisers multiply by the hoisted reciprocal of the scale, round with rintf
+//     (round-half-to-even, as torch.round in uniform.py:31-36) and clamp to [-128, 127];
 //   * softmax in fp32 (online, exp of x - max as the reference), P.V on fp16 MFMA with P split
 //     hi + lo (both fp16; |P - hi - lo| ~ 2^-22 |P|) and the exact int8 V codes as fp16.
 // Layout: S^T = K.Q^T per 16-key block (lane = one query, 4 keys), so P^T feeds the P.V MFMA's B

@@ -805,7 +805,7 @@ class W8A8Engine:
         xn = torch.empty_like(x)
         ao = torch.empty_like(x)
         v16buf = None
-        split = self._row_split(gh)
+        split = self._row_split(gh, gw, b)
         if taps is None and split:
             s_x = self._blocks_row_lanes(x, xn, ao, b, gh, gw, c, split)
             return self._neck(x, s_x, b, gh, gw)
@@ -843,10 +843,15 @@ class W8A8Engine:
             tap(pre + "qact4", x.view(b, gh, gw, c), s_x)
         return self._neck(x, s_x, b, gh, gw)
 
-    def _row_split(self, gh: int) -> int:
+    def _row_split(self, gh: int, gw: Optional[int] = None, b: int = 1) -> int:
         """First grid row of the second row lane (0: one chain): the window boundary nearest the
-        middle, so every window lies in one lane."""
-        if self.row_lanes <= 1:
+        middle, so every window lies in one lane.  One chain as well for what the lanes do not
+        cover: a batch other than 1, and global blocks on a grid other than 64 x 64 (the global
+        attention takes a query row range on that grid only).  ``gw`` defaults to a square grid."""
+        gw = gh if gw is None else gw
+        if self.row_lanes <= 1 or b != 1:
+            return 0
+        if (gh, gw) != (64, 64) and any(bl["window"] == 0 for bl in self.blocks):
             return 0
         wins = {bl["window"] for bl in self.blocks if bl["window"] > 0}
         step = max(wins) if wins else 1

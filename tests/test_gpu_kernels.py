@@ -329,7 +329,10 @@ def _attn_case(b, h, w, heads, d, window, seed):
         o = sam_ref.attention_core(qkvw, heads, t(rph).float(), t(rpw).float())
         ref = sam_ref.window_unpartition(o, window, pad_hw, (h, w)).numpy()
     else:
-        ref = sam_ref.attention_core(t(qkv16).float(), heads, t(rph).float(), t(rpw).float()).numpy()
+        # one head at a time: the (images, L, L) score tensors of a 64 x 64 grid stay at ~100 MB
+        q5 = t(qkv16).float().view(b, h, w, 3, heads, d)
+        ref = torch.cat([sam_ref.attention_core(q5[:, :, :, :, i].reshape(b, h, w, 3 * d), 1, t(rph).float(),
+                                                t(rpw).float()) for i in range(heads)], dim=-1).numpy()
     return qkv16, bq, rph, rpw, ref
 
 
@@ -346,6 +349,23 @@ def _attn_case(b, h, w, heads, d, window, seed):
     (1, 64, 64, 8, 80, 0),
     (1, 64, 64, 1, 80, 0),      # heads * B == 1: the 3-D grid launch (no XCD remap)
     (1, 32, 32, 1, 64, 0),
+    # streaming kernel on the XCD-remapped 1-D grid (heads * B % 8 == 0, not the 32x32-MFMA kernel):
+    # the block -> (head, image) decode; heads and images are drawn independently, so a wrong
+    # decode permutes them visibly
+    (1, 32, 32, 8, 64, 0),      # one (image, head) pair per XCD
+    (2, 32, 32, 8, 64, 0),      # two pairs per XCD, the image changes inside an XCD's range
+    (3, 32, 32, 8, 80, 0),      # three pairs per XCD, head dim 80
+    (1, 64, 64, 8, 64, 0),      # S = 64 at head dim 64 (vit_l's global blocks)
+    (2, 64, 64, 12, 64, 0),     # vit_b B = 2: 24 pairs, heads not a multiple of 8
+    # resident kernel with a runtime side < 16 (slots beyond the row masked at run time)
+    (2, 12, 12, 2, 64, 0),
+    (1, 15, 15, 1, 80, 0),
+    (2, 8, 8, 2, 80, 0),
+    # windows other than 14: resident kernel, window partitioning, pad tokens = bias, ragged grids
+    (1, 20, 33, 2, 64, 8),
+    (2, 20, 20, 2, 80, 16),
+    (1, 20, 33, 3, 80, 7),
+    (1, 30, 17, 2, 64, 15),
 ])
 def test_rel_attention(cuda, b, h, w, heads, d, window):
     from samq import ops
@@ -365,6 +385,9 @@ def test_rel_attention(cuda, b, h, w, heads, d, window):
     (2, 64, 64, 16, 80, 0),     # ViT-H global lane (streaming kernel)
     (1, 20, 33, 3, 64, 14),     # ragged grid, vit_b head dim
     (3, 16, 16, 2, 80, 0),      # resident small global grid
+    (2, 32, 32, 8, 64, 0),      # streaming kernel, XCD-remapped 1-D grid
+    (1, 20, 33, 2, 64, 8),      # resident kernel, window 8 on a ragged grid
+    (2, 12, 12, 2, 64, 0),      # resident kernel, runtime side 12
 ])
 def test_rel_attention_q_out(cuda, b, h, w, heads, d, window):
     """samq_rel_attention_q (the W4A8 proj-input QAct folded into the attention store) quantises the
@@ -515,6 +538,26 @@ def test_conv_ops_reject_bad_shapes(cuda):
     with pytest.raises((AssertionError, NotImplementedError)):
         ops.conv3x3_nhwc(torch.zeros(1, 8, 8, 48, dtype=torch.float16, device=cuda),
                          torch.zeros(128, 3, 3, 48, dtype=torch.float16, device=cuda))
+
+
+@pytest.mark.parametrize("h,w,heads,d,window", [
+    (16, 20, 2, 64, 0),     # global H != W
+    (20, 20, 2, 64, 0),     # global side 20: neither <= 16 nor 32 nor 64
+    (48, 48, 1, 64, 0),     # global side 48
+    (20, 20, 2, 64, 17),    # window 17
+    (16, 16, 2, 72, 0),     # head dim 72
+])
+def test_rel_attention_rejects_unsupported_geometry(cuda, h, w, heads, d, window):
+    """Geometries no fp16 attention kernel covers are refused, by both the fp16 and the int8 store."""
+    from samq import ops
+    c = heads * d
+    side = window or h
+    z = lambda *s: torch.zeros(s, dtype=torch.float16, device=cuda)
+    args = (z(1, h, w, 3 * c), z(3 * c), z(2 * side - 1, d), z(2 * side - 1, d), heads, window, d ** -0.5)
+    with pytest.raises(NotImplementedError):
+        ops.rel_attention(*args)
+    with pytest.raises(NotImplementedError):
+        ops.rel_attention(*args, out_scale=0.01)
 
 
 # ----------------------------------------------------------------------------- LayerNorm fold

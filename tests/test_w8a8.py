@@ -359,53 +359,287 @@ def test_quantize_and_layernorm_q(cuda):
             assert torch.equal(o2.cpu(), out.cpu()), rpw
 
 
-def _attn_ref(qkv_codes, bias, relh, relw, heads, window, s_qkv, s1, s2, s_o):
-    """fq_vit Attention core (oracle F semantics) on fake-quant qkv values, with windowing."""
+def _attn_ref(qkv_codes, bias, relh, relw, heads, window, s_qkv, s1, s2, s_o, dtype=torch.float32, fq1=None,
+              fq2=None, codes2=None):
+    """fq_vit Attention core (oracle F semantics) on fake-quant qkv values, with windowing.
+    ``dtype``: the precision the whole graph is evaluated in.  ``fq1`` / ``fq2``: stand-ins for the
+    fake quantiser of the two score QActs (a deliberately wrong one, to measure what a test can
+    see); ``codes2``: a list that receives the second score quantiser's codes.  ``bias`` None: the
+    pad tokens are zero codes.  The scores are evaluated a few (image, head) pairs at a time, so
+    a 64 x 64 grid in float64 stays within a few hundred MB."""
     b, h, w, c3 = qkv_codes.shape
     c = c3 // 3
     d = c // heads
-    qkv = torch.from_numpy(qkv_codes.astype(np.float32) * s_qkv)
+    fq1, fq2 = fq1 or fq_ref.fake_quant, fq2 or fq_ref.fake_quant
+    ts = lambda s: torch.tensor(float(s), dtype=dtype)   # the scales are fp32 values: exact in either dtype
+    qkv = torch.from_numpy(qkv_codes.astype(np.float32)).to(dtype) * ts(s_qkv)
     if window > 0:
         # pad tokens project the zero-padded LN output: qkv = bias, then attn.qact1
-        pad_val = fq_ref.fake_quant(torch.from_numpy(bias), torch.tensor(s_qkv))
+        pad_val = fq_ref.fake_quant(torch.from_numpy(bias).to(dtype) if bias is not None else
+                                    torch.zeros(c3, dtype=dtype), ts(s_qkv))
         hp, wp = -(-h // window) * window, -(-w // window) * window
         full = pad_val.expand(b, hp, wp, c3).clone()
         full[:, :h, :w] = qkv
         qkv, _ = sam_ref.window_partition(full, window)
     bq, hh, ww, _ = qkv.shape
-    t = qkv.reshape(bq, hh * ww, 3, heads, d).permute(2, 0, 3, 1, 4)
-    q, k, v = t.reshape(3, bq * heads, hh * ww, d).unbind(0)
-    sc = (q * (d ** -0.5)) @ k.transpose(-2, -1)
-    sc = fq_ref.fake_quant(sc, torch.tensor(s1))
-    rh, rw = sam_ref.rel_bias(q.reshape(bq * heads, hh, ww, d), torch.from_numpy(relh), torch.from_numpy(relw), hh, ww)
-    sc = (sc.view(bq * heads, hh, ww, hh, ww) + rh[..., :, None] + rw[..., None, :]).view(bq * heads, hh * ww, hh * ww)
-    sc = fq_ref.fake_quant(sc, torch.tensor(s2))
-    o = (torch.softmax(sc, -1) @ v).view(bq, heads, hh, ww, d).permute(0, 2, 3, 1, 4).reshape(bq, hh, ww, c)
+    n, ll = bq * heads, hh * ww
+    t = qkv.reshape(bq, ll, 3, heads, d).permute(2, 0, 3, 1, 4)
+    q, k, v = t.reshape(3, n, ll, d).unbind(0)
+    rph, rpw = torch.from_numpy(relh).to(dtype), torch.from_numpy(relw).to(dtype)
+    o = torch.empty((n, ll, d), dtype=dtype)
+    step = max(1, (1 << 24) // (ll * ll))
+    for i in range(0, n, step):
+        qi, ki, vi = q[i:i + step], k[i:i + step], v[i:i + step]
+        m = qi.shape[0]
+        sc = (qi * (d ** -0.5)) @ ki.transpose(-2, -1)
+        sc = fq1(sc, ts(s1))
+        rh, rw = sam_ref.rel_bias(qi.reshape(m, hh, ww, d), rph, rpw, hh, ww)
+        sc = (sc.view(m, hh, ww, hh, ww) + rh[..., :, None] + rw[..., None, :]).view(m, ll, ll)
+        sc = fq2(sc, ts(s2))
+        if codes2 is not None:
+            codes2.append(torch.round(sc / ts(s2)).to(torch.int16))
+        o[i:i + step] = torch.softmax(sc, -1) @ vi
+    o = o.view(bq, heads, hh, ww, d).permute(0, 2, 3, 1, 4).reshape(bq, hh, ww, c)
     if window > 0:
         o = sam_ref.window_unpartition(o, window, (hp, wp), (h, w))
-    return np.clip(np.round((o / s_o).numpy()), -128, 127)
+    return np.clip(np.round((o / ts(s_o)).numpy()), -128, 127)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("b,hw,window", [(1, 20, 14), (2, 14, 14), (1, 16, 0), (1, 32, 0), (1, 64, 0)])
-def test_rel_attention_q8(cuda, b, hw, window):
-    from samq import ops
-    heads, d = 2 if hw == 64 else 3, 64
+_Q8_SCALES = (np.float32(0.02), np.float32(2.0 / 127.5), np.float32(6.0 / 127.5), np.float32(2.6 / 127.5))
+
+
+def _q8_inputs(b, h, w, heads, window, seed):
+    """Random full-range codes, N(0, 0.5) tables, N(0, 0.3) bias; the scales (s_qkv, s_a1, s_a2, s_out)
+    are _Q8_SCALES, chosen like minmax calibration would (max |score| / 127.5)."""
+    d = 64
     c = heads * d
-    rng = np.random.Generator(np.random.PCG64(hw + window))
-    qkv = rng.integers(-128, 128, (b, hw, hw, 3 * c), dtype=np.int8)
-    side = window or hw
+    rng = np.random.Generator(np.random.PCG64(seed))
+    qkv = rng.integers(-128, 128, (b, h, w, 3 * c), dtype=np.int8)
+    side = window or h
     relh = (rng.standard_normal((2 * side - 1, d), dtype=np.float32) * 0.5).astype(np.float32)
     relw = (rng.standard_normal((2 * side - 1, d), dtype=np.float32) * 0.5).astype(np.float32)
     bias = (rng.standard_normal(3 * c, dtype=np.float32) * 0.3).astype(np.float32)
-    s_qkv = np.float32(0.02)
-    # score scales chosen like minmax calibration would (max |score| / 127.5)
-    s1, s2, s_o = np.float32(2.0 / 127.5), np.float32(6.0 / 127.5), np.float32(2.6 / 127.5)
-    ref = _attn_ref(qkv, bias, relh, relw, heads, window, s_qkv, s1, s2, s_o)
-    out = ops.rel_attention_q8(torch.from_numpy(qkv).to(cuda), torch.from_numpy(bias).to(cuda),
-                               torch.from_numpy(relh).to(cuda), torch.from_numpy(relw).to(cuda), heads, window,
-                               d ** -0.5, float(s_qkv), float(s1), float(s2), float(s_o))
+    return qkv, bias, relh, relw
+
+
+def _q8_launch(cuda, qkv, bias, relh, relw, heads, window, scales, **kw):
+    from samq import ops
+    dev = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.from_numpy(a)).to(cuda)
+    return ops.rel_attention_q8(dev(qkv), dev(bias), dev(relh), dev(relw), heads, window, 64 ** -0.5,
+                                *(float(s) for s in scales), **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("b,hw,window", [
+    (1, 20, 14), (2, 14, 14), (1, 16, 0), (1, 32, 0), (1, 64, 0),
+    # windows other than 14: the resident kernel, 13 waves (L <= 208) ...
+    (1, 20, 7), (1, 20, 8), (1, 20, 12), (1, 20, 13),
+    # ... and 16 waves (windows 15 and 16); (2, 16, 16): one unpadded 16 x 16 window per image
+    (1, 20, 15), (1, 20, 16), (2, 16, 16),
+    # global, streaming kernel on ragged grids: the last 64-key chunk is partly past L (10: L = 100,
+    # 17: 289, 20: 400, 24: 576 = 9 chunks exactly but key rows straddle chunks, 48: 2304) and the
+    # last query tile is partly (or, per wave, wholly) past L
+    (1, 10, 0), (1, 17, 0), (1, 20, 0), (1, 24, 0), (1, 48, 0),
+])
+def test_rel_attention_q8(cuda, b, hw, window):
+    heads = {64: 2, 48: 1}.get(hw, 3)
+    qkv, bias, relh, relw = _q8_inputs(b, hw, hw, heads, window, hw + window)
+    ref = _attn_ref(qkv, bias, relh, relw, heads, window, *_Q8_SCALES)
+    out = _q8_launch(cuda, qkv, bias, relh, relw, heads, window, _Q8_SCALES)
     _codes_close(out.cpu().numpy(), ref, 5e-3, f"attention_q8 {b}x{hw} win {window}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h,w,with_bias", [(20, 33, True), (20, 20, False)])
+def test_rel_attention_q8_window14_geometries(cuda, h, w, with_bias):
+    """The 14-window kernel on a non-square grid (2 x 3 windows, pads on both sides) and with
+    qkv_bias = None (pad tokens are zero codes; the reference pads with a zero bias).  Inputs and
+    bound of test_rel_attention_q8."""
+    heads = 3
+    qkv, bias, relh, relw = _q8_inputs(1, h, w, heads, 14, h + w + 14)
+    if not with_bias:
+        bias = None
+    ref = _attn_ref(qkv, bias, relh, relw, heads, 14, *_Q8_SCALES)
+    out = _q8_launch(cuda, qkv, bias, relh, relw, heads, 14, _Q8_SCALES)
+    _codes_close(out.cpu().numpy(), ref, 5e-3, f"attention_q8 1x{h}x{w} win 14 bias {with_bias}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("b,heads", [(2, 1), (1, 3)])
+def test_rel_attention_q8_row64_batch_heads(cuda, b, heads):
+    """The 64 x 64 global kernel beyond B = 1, heads = 2: two images (heads = 1) and three heads,
+    against the reference (inputs and bound of test_rel_attention_q8).  At B = 2 also: V staged from
+    an fp16 copy of its codes (v16) and the row ranges (0, 28) + (28, 36), both bit-identical to the
+    full int8-V launch."""
+    hw = 64
+    qkv, bias, relh, relw = _q8_inputs(b, hw, hw, heads, 0, 64 + 10 * b + heads)
+    ref = _attn_ref(qkv, bias, relh, relw, heads, 0, *_Q8_SCALES)
+    dq, dh, dw = (torch.from_numpy(a).to(cuda) for a in (qkv, relh, relw))
+    full = _q8_launch(cuda, dq, None, dh, dw, heads, 0, _Q8_SCALES)
+    _codes_close(full.cpu().numpy(), ref, 5e-3, f"attention_q8 row64 B {b} heads {heads}")
+    if b == 2:
+        c = heads * 64
+        v16 = dq[..., 2 * c:].to(torch.float16).contiguous()
+        o16 = _q8_launch(cuda, dq, None, dh, dw, heads, 0, _Q8_SCALES, v16=v16)
+        torch.cuda.synchronize()
+        assert torch.equal(o16, full)
+        out = torch.zeros_like(full)
+        for r0, n in ((0, 28), (28, 36)):
+            _q8_launch(cuda, dq, None, dh, dw, heads, 0, _Q8_SCALES, out=out, rows=(r0, n))
+        torch.cuda.synchronize()
+        assert torch.equal(out, full)
+
+
+@pytest.mark.gpu
+def test_rel_attention_q8_refusals(cuda):
+    """Geometries no kernel covers are refused (SAMQ_ERR_UNSUPPORTED), not computed wrongly."""
+    def run(b, h, w, heads, d, window, **kw):
+        from samq import ops
+        c = heads * d
+        side = window or h
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=cuda)
+        qkv = torch.zeros((b, h, w, 3 * c), dtype=torch.int8, device=cuda)
+        return ops.rel_attention_q8(qkv, z(3 * c), z(2 * side - 1, d), z(2 * side - 1, d), heads, window, d ** -0.5,
+                                    0.02, 0.02, 0.05, 0.02, **kw)
+    run(1, 32, 32, 1, 64, 0)                       # the whole H = 32 grid is served
+    for args, kw in [((1, 32, 32, 1, 64, 0), dict(rows=(0, 16))),   # partial global row range off the 64 x 64 grid
+                     ((1, 16, 20, 1, 64, 0), {}),                   # global H != W
+                     ((1, 65, 65, 1, 64, 0), {}),                   # H = 65
+                     ((1, 20, 20, 1, 64, 17), {}),                  # window 17
+                     ((1, 16, 16, 2, 32, 0), {})]:                  # head dim 32
+        with pytest.raises(NotImplementedError):
+            run(*args, **kw)
+    torch.cuda.synchronize()
+
+
+def _exact_attn_inputs(b, h, w, heads, window, variant, seed):
+    """W8A8 attention inputs on which every score-side operation is exact in fp32 in any summation
+    order, so the two score quantisers see exactly representable arguments -- many of them exact
+    .5 ties or beyond the clamp -- and a kernel's score codes can differ from the reference's only
+    if its rounding mode or clamp ends do.
+
+    d = 64, sm_scale = 2^-3, s_qkv = 2^-5: q.k * scale = int * 2^-13 (|int| <= 2^20).  The rel-pos
+    tables are integers in [-8, 8] times 2^-4 (exact in fp16 too, for the hi / lo table split of
+    the MFMA rel path), so rel_h, rel_w = int * 2^-9 (|int| <= 2^16).  qkv_bias holds half-integers
+    times s_qkv ((2k + 1) / 2 * 2^-5, |k| <= 40): the pad-token codes sit on ties, and a few values
+    lie beyond +-128.5 s_qkv so a pad code clamps.
+      "fine":       q, k codes in [-16, 16), v full range; s_a1 = 2^-9, s_a2 = 2^-6, s_out = 2^-3 / S:
+                    1/16 of the first quantiser's arguments and 1/8 of the second's are exact ties,
+                    few saturate;
+      "saturating": all codes full range, the first three tokens' q and k all 127 and the next two
+                    all -128; s_a1 = 2^-6, s_a2 = 2^-4, s_out = 2^-6: a large share of the scores
+                    clamps at both ends of both quantisers.
+    Returns (qkv, bias, relh, relw, (s_qkv, s_a1, s_a2, s_out))."""
+    d = 64
+    c = heads * d
+    side = window or h
+    rng = np.random.Generator(np.random.PCG64(seed))
+    relh = (rng.integers(-8, 9, (2 * side - 1, d)) * 2.0 ** -4).astype(np.float32)
+    relw = (rng.integers(-8, 9, (2 * side - 1, d)) * 2.0 ** -4).astype(np.float32)
+    s_qkv = np.float32(2.0 ** -5)
+    kb = rng.integers(-40, 41, 3 * c).astype(np.float64)
+    far = rng.random(3 * c) < 1.0 / 16
+    kb[far] = rng.choice(np.array([-141.0, -130.0, -129.0, 128.0, 129.0, 140.0]), int(far.sum()))
+    bias = ((2 * kb + 1) / 2 * 2.0 ** -5).astype(np.float32)
+    if variant == "fine":
+        qkv = rng.integers(-128, 128, (b, h, w, 3 * c), dtype=np.int8)
+        qkv[..., :2 * c] = rng.integers(-16, 16, (b, h, w, 2 * c), dtype=np.int8)
+        scales = (s_qkv, np.float32(2.0 ** -9), np.float32(2.0 ** -6), np.float32(2.0 ** -3 / side))
+    else:
+        assert variant == "saturating"
+        qkv = rng.integers(-128, 128, (b, h, w, 3 * c), dtype=np.int8)
+        tok = qkv.reshape(b, h * w, 3 * c)
+        tok[:, 0:3, :2 * c] = 127
+        tok[:, 3:5, :2 * c] = -128
+        scales = (s_qkv, np.float32(2.0 ** -6), np.float32(2.0 ** -4), np.float32(2.0 ** -6))
+    return qkv, bias, relh, relw, scales
+
+
+def _fq_half_away(x, s):
+    """A WRONG fake quantiser: round half away from zero instead of half to even."""
+    r = x / s
+    return torch.clamp(torch.sign(r) * torch.floor(torch.abs(r) + 0.5), -128, 127) * s
+
+
+def _fq_low127(x, s):
+    """A WRONG fake quantiser: symmetric clamp [-127, 127]."""
+    return torch.clamp(torch.round(x / s), -127, 127) * s
+
+
+@pytest.mark.parametrize("variant", ["fine", "saturating"])
+@pytest.mark.parametrize("b,hw,window", [(1, 20, 14), (1, 16, 0)])
+def test_exact_attn_inputs_pin_the_quantisers(b, hw, window, variant):
+    """CPU: what test_rel_attention_q8_exact_ties relies on.  On _exact_attn_inputs the float32 and
+    float64 evaluations of the reference give identical second-quantiser codes (every score-side
+    value is exact) and output codes that differ in at most 1e-4 of the positions, while a
+    reference with round-half-away at the first score quantiser, at the second, or with the low
+    clamp at -127 differs from the correct one in more than 1e-3 of the output codes -- ten times the
+    GPU test's bound.
+
+    One combination cannot reach 1e-3 and is held to the GPU test's own bound instead: round-half-away
+    at the FIRST quantiser on the "saturating" inputs.  There q.k * scale / s_a1 has a standard
+    deviation of ~340 codes, so ~70 % of the first quantiser's arguments lie beyond the clamp and
+    only 1/128 of the rest are ties; one of those moves the second quantiser's argument by a
+    quarter of a code.  Measured over seeds 0-3: 9e-5 to 8e-4 of the output codes.  The "fine"
+    variant is the one that pins that rounding mode (> 6e-3 on both geometries)."""
+    heads = 2
+    qkv, bias, relh, relw, scales = _exact_attn_inputs(b, hw, hw, heads, window, variant, seed=hw + window)
+    c32, c64 = [], []
+    ref32 = _attn_ref(qkv, bias, relh, relw, heads, window, *scales, codes2=c32)
+    ref64 = _attn_ref(qkv, bias, relh, relw, heads, window, *scales, dtype=torch.float64, codes2=c64)
+    assert all(torch.equal(a, b_) for a, b_ in zip(c32, c64))
+    codes = torch.cat([t.reshape(-1) for t in c64])
+    hi, lo = float((codes == 127).double().mean()), float((codes == -128).double().mean())
+    own = float((ref32 != ref64).mean())
+    print(f"\n[exact {variant} {b}x{hw} win {window}] second-quantiser codes at 127: {hi:.3f}, at -128: {lo:.3f}; "
+          f"output codes fp32 vs fp64 {own:.2e}")
+    assert np.abs(ref32 - ref64).max() <= 1 and own <= 1e-4
+    assert hi > 0 and lo > 0    # both clamp ends are exercised
+    for what, kw in [("half-away at quantiser 1", dict(fq1=_fq_half_away)),
+                     ("half-away at quantiser 2", dict(fq2=_fq_half_away)),
+                     ("low clamp -127", dict(fq1=_fq_low127, fq2=_fq_low127))]:
+        wrong = _attn_ref(qkv, bias, relh, relw, heads, window, *scales, dtype=torch.float64, **kw)
+        frac = float((wrong != ref64).mean())
+        print(f"    {what}: {frac:.2e} of the output codes change")
+        weak = variant == "saturating" and what == "half-away at quantiser 1"   # see the docstring
+        assert frac > (1e-4 if weak else 10 * 1e-4), what
+
+
+_EXACT_GEOMETRIES = {
+    "win14": (2, 20, 33, 2, 14),      # rel_attention_q8_win_kernel<14, 7>, ragged non-square grid
+    "win8": (1, 20, 20, 2, 8),        # resident kernel, 13 waves
+    "win16": (1, 20, 20, 2, 16),      # resident kernel, 16 waves
+    "glob20": (1, 20, 20, 2, 0),      # streaming kernel, ragged last chunk / query tile
+    "glob32": (1, 32, 32, 2, 0),      # streaming kernel
+    "glob64": (1, 64, 64, 2, 0),      # row64 kernel, int8 V and fp16 V
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["fine", "saturating"])
+@pytest.mark.parametrize("geom", list(_EXACT_GEOMETRIES))
+def test_rel_attention_q8_exact_ties(cuda, geom, variant):
+    """Rounding mode and clamp ends of the two score quantisers (and of the pad-token codes), per
+    kernel: on _exact_attn_inputs -- exact ties and saturating scores -- every output code is
+    within +-1 of the float64 reference and at most 1e-4 of them differ.  The bound is the stage
+    figure of test_w8a8_stage_local_parity; the fp32 reference's own distance to fp64 on these
+    inputs is <= 2e-5 and a wrong rounding mode or clamp end moves > 1e-3 of the codes
+    (test_exact_attn_inputs_pin_the_quantisers).
+    Measured on gfx950 (share of differing codes, all within +-1): largest 2.29e-5 (glob64 fine, the
+    same with int8 and fp16 V); glob32 7.6e-6 / 1.5e-5 (fine / saturating), glob64 saturating 1.9e-6,
+    win14 fine 5.9e-6, every other case 0."""
+    b, h, w, heads, window = _EXACT_GEOMETRIES[geom]
+    qkv, bias, relh, relw, scales = _exact_attn_inputs(b, h, w, heads, window, variant, seed=h + w + window)
+    ref = _attn_ref(qkv, bias, relh, relw, heads, window, *scales, dtype=torch.float64)
+    dq = torch.from_numpy(qkv).to(cuda)
+    launches = [("int8 V", {})]
+    if geom == "glob64":
+        launches.append(("fp16 V", dict(v16=dq[..., 2 * heads * 64:].to(torch.float16).contiguous())))
+    for what, kw in launches:
+        out = _q8_launch(cuda, dq, bias, relh, relw, heads, window, scales, **kw).cpu().numpy()
+        d = np.abs(out.astype(np.int64) - ref.astype(np.int64))
+        print(f"\n[exact ties {geom} {variant} {what}] codes differing {float((d > 0).mean()):.2e}, max |dcode| {d.max()}")
+        _codes_close(out, ref, 1e-4, f"attention_q8 exact {geom} {variant} {what}")
 
 
 @pytest.mark.gpu
@@ -503,6 +737,24 @@ def test_w8a8_row_lanes_bit_identical(cuda):
         graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(gout, ref)
+
+
+@pytest.mark.gpu
+def test_w8a8_row_lanes_fall_back_to_one_chain(cuda):
+    """The row lanes cover B = 1 on the 64 x 64 grid only: with row_lanes = 2 a B = 2 forward (and a
+    grid whose global blocks are not 64 x 64) runs the one chain -- the same codes bit for bit, not
+    a NotImplementedError partway through the forward."""
+    from samq.synthetic import random_fq_encoder
+    enc = random_fq_encoder("vit_b", device=cuda)
+    eng = enc.engine()
+    img = torch.randn((2, 3, 1024, 1024), generator=torch.Generator(device=cuda).manual_seed(6), device=cuda)
+    eng.row_lanes = 1
+    ref = eng(img).clone()
+    eng.row_lanes = 2
+    assert eng._row_split(64, 64, b=2) == 0 and eng._row_split(32, 32, b=1) == 0 and eng._row_split(64, 64, b=1) == 28
+    got = eng(img)
+    torch.cuda.synchronize()
+    assert torch.equal(got, ref)
 
 
 # ----------------------------------------------------------------------------- GPU: encoder
