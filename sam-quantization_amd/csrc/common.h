@@ -108,6 +108,19 @@ __device__ __forceinline__ float2_t gelu_r16_2(float2_t x) {
   return __builtin_elementwise_fma(-ax, r, m);
 }
 
+// GELU(x) = relu(x) - |x| * erfc(|x| / sqrt2) / 2 with the library erfc: RELATIVE accuracy in the
+// negative tail, where GELU(x) -> -0.  For fp16 outputs (the int8 GEMMs' BIAS_GELU epilogue): there
+// one fp16 step (6e-8 .. 2.4e-7 for |GELU| < 4.9e-4, x in [-5, -3.6]) is finer than the absolute
+// error of the A&S forms above, whose results landed 2 .. 8 fp16 steps from float16(GELU_erf(x))
+// on 1 .. 2 % of N(0, 3) inputs.  Same relu - |x| r structure as gelu_r16_2.
+__device__ __forceinline__ float2_t gelu_erfc2(float2_t x) {
+  const float2_t ax = __builtin_elementwise_abs(x);
+  const float2_t z = ax * (float2_t)(0.70710678118654752440f);
+  const float2_t r = {0.5f * erfcf(z.x), 0.5f * erfcf(z.y)};
+  const float2_t m = {fmaxf(x.x, 0.0f), fmaxf(x.y, 0.0f)};
+  return __builtin_elementwise_fma(-ax, r, m);
+}
+
 // gelu_r16_2 on N pairs at once, stage by stage across the pairs: the per-pair form is a chain of
 // ~12 dependent packed ops (Horner, four squarings, rcp), which at two waves per SIMD left the VALU
 // waiting on each result (the compiler padded the chains with s_nop); N independent chains in

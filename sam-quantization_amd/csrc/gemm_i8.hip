@@ -145,7 +145,12 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
                                                                  (float2_t)(cb[t]));
         }
       }
-      if constexpr (GELU) gelu_r16_n<2 * TN>(y);
+      if constexpr (EPI == SAMQ_EPI_BIAS_GELU) {   // fp16 out: within one fp16 step down the negative tail
+#pragma unroll
+        for (int n = 0; n < 2 * TN; ++n) y[n] = gelu_erfc2(y[n]);
+      } else if constexpr (GELU) {
+        gelu_r16_n<2 * TN>(y);
+      }
 #pragma unroll
       for (int r = r0; r < r0 + 4; r += 2) {
         const int rl = (r & 3) + 8 * (r >> 2) + 4 * hsel;
@@ -239,6 +244,9 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
             }
             *(u32x4*)((int8_t*)Cout + (int64_t)row * ldc + col_base + 16 * c16) = o;
             if constexpr (EPI == SAMQ_EPI_Q8) {
+              // v16_col0 is a multiple of 64 (samq_w8a8_gemm_v16): a wave of at most 64 columns, at a
+              // multiple of WN, lies wholly on one side of it
+              static_assert(WN <= 64 && 64 % WN == 0, "v16 store: a wave's columns must not straddle v16_col0");
               if (ep_args.v16 && col_base >= ep_args.v16_col0) {   // (uniform: a wave's columns are in one third)
                 half8_t h0, h1;
 #pragma unroll

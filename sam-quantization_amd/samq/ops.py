@@ -359,6 +359,8 @@ def layernorm_q(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: f
     row sums); ``zero_rows`` (int32 [rows]) is zeroed on the way."""
     if rowsum is not None:
         return _layernorm_q_rs(x, gamma, beta, eps, in_scale, out_scale, out, rows_per_wave, rowsum, zero_rows)
+    if zero_rows is not None:
+        raise AssertionError("layernorm_q: zero_rows is zeroed on the row-sum path only (pass rowsum too)")
     _need_cuda(x, gamma, beta)
     c = x.shape[-1]
     assert x.is_contiguous() and gamma.dtype == torch.float32 and beta.dtype == torch.float32
@@ -526,6 +528,8 @@ def w4a8_gemm(a, wpacked3, wscale, qzeros, n, bias=None, epilogue=EPI_BIAS, a_sc
                        cfg=cfg)
     if groupsize <= 0 or groupsize % 128:
         raise NotImplementedError("w4a8_gemm: grouped weights need groupsize % 128 == 0 (the int8 K tile)")
+    if rowsum is not None or rowsum_out is not None:
+        raise AssertionError("w4a8_gemm: rowsum / rowsum_out are per-channel only (grouped weights have no row-sum path)")
     _need_cuda(a, wpacked3, wscale, bias, qzeros)
     assert a.dtype == torch.int8 and wscale.dtype == torch.float32
     assert bias is None or bias.dtype == torch.float32
