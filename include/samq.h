@@ -220,6 +220,31 @@ size_t samq_minmax_workspace(int64_t rows, int C, int axis);
 int samq_minmax(const void* x, int64_t rows, int C, int in_f16, int axis, float* max_io, float* min_io,
                 int init, float* workspace, size_t workspace_floats, hipStream_t stream);
 
+/* Exact order statistics of a flat tensor -- what fq_vit PercentileObserver.update takes from
+ * torch.quantile / np.percentile (observer/percentile.py:27-39).  x: n values, f32 (f16 with
+ * in_f16, converted exactly); ranks: HOST array of nranks (1..4) zero-based ranks in [0, n);
+ * out (device, f32[nranks]) receives the value at each rank of the sorted tensor; nan_flag
+ * (device int) is set to 1 if any input is NaN (out is then unspecified), else 0.  +-0 compare
+ * equal, either may be returned.  Radix select on the order-preserving uint32 image of the
+ * floats: three histogram passes (11 / 11 / 10 bits) that serve every rank, the bin selection
+ * in between on the device; nothing is read back.  1 <= n < 2^40.  The workspace
+ * (samq_order_stats_workspace(n, nranks) bytes, 8-byte aligned) is the caller's. */
+size_t samq_order_stats_workspace(int64_t n, int nranks);
+int samq_order_stats(const void* x, int64_t n, int in_f16, const int64_t* ranks, int nranks, float* out,
+                     int* nan_flag, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+/* The fq_vit OmseObserver candidate scores in one read of the tensor (observer/omse.py:45-49,
+ * lp_loss observer/utils.py:9).  cand: device f32 [ncand][2] = (scale, zero_point), ncand 1..96.
+ * sums (device f64[ncand]): sums[c] = sum_i e_ci with, in f32 and rounded step by step as torch's
+ * separate ops do (IEEE division, no fused multiply-add),
+ *   q = clamp(rint(x_i / s_c + zp_c), qmin, qmax);  xq = (q - zp_c) * s_c;  d = x_i - xq;  e = d * d,
+ * accumulated in float64 in a fixed order (lane, wave, workgroup, then a second-pass fold): the
+ * same sums on every run.  x f32 (f16 with in_f16).  The workspace
+ * (samq_omse_scores_workspace(n, ncand) bytes, 8-byte aligned) is the caller's. */
+size_t samq_omse_scores_workspace(int64_t n, int ncand);
+int samq_omse_scores(const void* x, int64_t n, int in_f16, const float* cand, int ncand, float qmin, float qmax,
+                     double* sums, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* Fused gated MLP in ONE launch: C f16 [M, N] = silu(A . Wg) * (A . Wu) with both int4 weight
  * sets in one packed matrix of 2N columns whose 32-column blocks alternate gate block j, up
  * block j (the samq_w4_repack layout-1 blocks interleaved; scales / qzeros interleaved the same

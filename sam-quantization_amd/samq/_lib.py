@@ -80,7 +80,11 @@ SIGNATURES = {
     "samq_quantize": (_i32, [_vp, _vp, _i64, _f32, _i32, _vp]),
     "samq_minmax_workspace": (ctypes.c_size_t, [_i64, _i32, _i32]),
     "samq_minmax": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp, ctypes.c_size_t, _vp]),
-    "samq_silu_mul": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "samq_order_stats_workspace": (ctypes.c_size_t, [_i64, _i32]),
+    "samq_order_stats": (_i32, [_vp, _i64, _i32, ctypes.POINTER(_i64), _i32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "samq_omse_scores_workspace": (ctypes.c_size_t, [_i64, _i32]),
+    "samq_omse_scores": (_i32, [_vp, _i64, _i32, _vp, _i32, _f32, _f32, _vp, _vp, ctypes.c_size_t, _vp]),
+    "samq_silu_mul":(_i32, [_vp, _vp, _vp, _i64, _vp]),
     "samq_w4a16_gated_mlp": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "samq_layernorm": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp]),
     "samq_layernorm_mean": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp]),

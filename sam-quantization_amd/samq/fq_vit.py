@@ -4,8 +4,9 @@ Mirrors (names, constructor arguments, flags, ``quantizer.scale`` buffers) the r
 ``fq_vit`` package so calibrated state dicts load unchanged:
 
 * ``Config`` (``fq_vit/config.py:4-43``), ``BIT_TYPE_DICT`` (``models/ptq/bit_type.py:7-47``);
-* ``MinmaxObserver`` (``observer/minmax.py:14-50``, ``observer/base.py:16-29``),
-  ``UniformQuantizer`` (``quantizer/uniform.py:9-45``, ``quantizer/base.py:15-49``);
+* ``MinmaxObserver`` (``observer/minmax.py:14-50``, ``observer/base.py:16-29``), ``EmaObserver``
+  (``observer/ema.py``), ``PercentileObserver`` (``observer/percentile.py``), ``OmseObserver``
+  (``observer/omse.py``), ``UniformQuantizer`` (``quantizer/uniform.py:9-45``, ``quantizer/base.py:15-49``);
 * ``QConv2d`` / ``QLinear`` / ``QAct`` / ``QIntLayerNorm`` / ``QIntSoftmax``
   (``models/ptq/layers.py:11-74, 160-200, 203-242, 245-258, 306-379``), ``QIntLayerNorm2D``
   (``models/sam/common.py:93-108``);
@@ -16,9 +17,18 @@ Mirrors (names, constructor arguments, flags, ``quantizer.scale`` buffers) the r
   ``model_close_calibrate`` / ``model_quant`` / ``model_dequant`` (``models/sam/sam.py:208-235``).
 
 Supported configuration = the one the reference's SAM path uses (``test_quant.py:229-231``):
-``Config(ptf=False, lis=False, quant_method="minmax")`` with ``BIT_TYPE_A = int8``: int8
-symmetric per-channel weights, int8 symmetric layer-wise activations (zero point 0), plain
-LayerNorm / softmax.  Other configurations raise ``NotImplementedError`` in quant mode.
+``Config(ptf=False, lis=False, quant_method=m)`` with ``BIT_TYPE_A = int8`` and ``m`` any of the
+four observers of ``test_quant.py:34-36`` -- ``minmax``, ``ema``, ``percentile``, ``omse``: int8
+symmetric per-channel weights (always minmax), int8 layer-wise activations, plain LayerNorm /
+softmax.  minmax, ema and percentile give symmetric activations (zero point 0) and run the fused
+engine.  omse searches an asymmetric range, so its zero points are non-zero: it calibrates (on the
+HIP observers) and runs the module graph, and the engine raises ``NotImplementedError`` for it, as
+for every other configuration (``ptf``, ``lis``, other bit types) in quant mode.
+
+Every observer has a torch path for CPU tensors (the reference's ops, bit for bit) and a HIP path
+for GPU tensors: ``samq_minmax`` (minmax, ema, omse's statistics), ``samq_order_stats`` (the exact
+order statistics behind percentile's quantiles, any size, nothing copied to the host) and
+``samq_omse_scores`` (omse's 90 candidate scores in one read of the tensor).
 
 Float and calibration forwards run the reference graph with torch ops (this is the observer
 pass, not the hot path).  In quant mode on a GPU the encoder's forward is the fused HIP engine
@@ -123,8 +133,12 @@ class MinmaxObserver:
             v = v.permute(0, 2, 3, 1)
         return v.reshape(-1, v.shape[-1]).transpose(0, 1)
 
+    # False: GPU tensors take the torch-op path as well (the reference's behaviour).  For measuring the
+    # HIP observers against it (tools/bench_calibration.py); calibration leaves it True.
+    use_hip = True
+
     def update(self, v: torch.Tensor) -> None:
-        if v.is_cuda:
+        if v.is_cuda and self.use_hip:
             return self._update_hip(v)
         v = self.reshape_tensor(v)
         cur_max, cur_min = v.max(dim=1).values, v.min(dim=1).values
@@ -134,13 +148,10 @@ class MinmaxObserver:
             self.max_val = self.max_val.max()
             self.min_val = self.min_val.min()
 
-    def _update_hip(self, v: torch.Tensor) -> None:
-        """GPU tensors: the same statistics from one HIP reduction (``samq_minmax``) on the
-        un-transposed layout -- rows of ``(out, -1)`` for weights, columns of the channel-last
-        ``(-1, C)`` view for activations, everything for layer_wise.  Bit-identical to the torch
-        path (max / min are exact); running values are f32 for f32 / f16 / bf16 inputs alike
-        (the torch path keeps the input dtype: same values, as the inputs convert exactly)."""
-        from . import ops, _lib
+    def _hip_view(self, v: torch.Tensor):
+        """The contiguous f32 / f16 (rows, C) view ``samq_minmax`` reads, the reduction axis for this
+        observer's calibration mode and the per-channel axis of the module type."""
+        from . import _lib
         v = v.detach()
         if v.dtype not in (torch.float32, torch.float16):
             v = v.float()
@@ -152,7 +163,16 @@ class MinmaxObserver:
                 v = v.permute(0, 2, 3, 1)
             x2d = v.reshape(-1, v.shape[-1]).contiguous()
             per = _lib.MM_PER_COL
-        axis = _lib.MM_ALL if self.calibration_mode == "layer_wise" else per
+        return x2d, (_lib.MM_ALL if self.calibration_mode == "layer_wise" else per), per
+
+    def _update_hip(self, v: torch.Tensor) -> None:
+        """GPU tensors: the same statistics from one HIP reduction (``samq_minmax``) on the
+        un-transposed layout -- rows of ``(out, -1)`` for weights, columns of the channel-last
+        ``(-1, C)`` view for activations, everything for layer_wise.  Bit-identical to the torch
+        path (max / min are exact); running values are f32 for f32 / f16 / bf16 inputs alike
+        (the torch path keeps the input dtype: same values, as the inputs convert exactly)."""
+        from . import ops, _lib
+        x2d, axis, per = self._hip_view(v)
         if self.max_val is not None:
             want = () if axis == _lib.MM_ALL else (x2d.shape[0] if per == _lib.MM_PER_ROW else x2d.shape[1],)
             if tuple(self.max_val.shape) != want or self.max_val.dtype != torch.float32 or not self.max_val.is_cuda:
@@ -177,11 +197,237 @@ class MinmaxObserver:
         return scale, zero_point
 
 
+def _uniform_params(obs, max_val, min_val):
+    """The scale / zero point tail shared by the ema and percentile observers (``ema.py:34-54``,
+    ``percentile.py:51-71``); the division as in ``MinmaxObserver.get_quantization_params``."""
+    qmax, qmin = obs.bit_type.upper_bound, obs.bit_type.lower_bound
+    if obs.symmetric:
+        scale = (torch.max(-min_val, max_val).double() / (float(qmax - qmin) / 2)).float()
+        scale.clamp_(obs.eps)
+        zero_point = torch.zeros_like(max_val, dtype=torch.int64)
+    else:
+        scale = ((max_val - min_val).double() / float(qmax - qmin)).float()
+        scale.clamp_(obs.eps)
+        zero_point = (qmin - torch.round(min_val / scale)).clamp_(qmin, qmax)
+    return scale, zero_point
+
+
+class EmaObserver(MinmaxObserver):
+    """``observer/ema.py:7-54``: running max / min as ``m + ema_sigma * (cur - m)``."""
+
+    def __init__(self, module_type, bit_type, calibration_mode, ema_sigma=0.01, permute=True):
+        super().__init__(module_type, bit_type, calibration_mode, permute=permute)
+        self.ema_sigma = ema_sigma
+
+    def update(self, v: torch.Tensor) -> None:
+        if v.is_cuda and self.use_hip:
+            return self._update_hip(v)
+        v = self.reshape_tensor(v)
+        cur_max, cur_min = v.max(dim=1).values, v.min(dim=1).values
+        self.max_val = cur_max if self.max_val is None else self.max_val +self.ema_sigma * (cur_max - self.max_val)
+        self.min_val = cur_min if self.min_val is None else self.min_val + self.ema_sigma * (cur_min - self.min_val)
+        if self.calibration_mode == "layer_wise":
+            self.max_val = self.max_val.max()
+            self.min_val = self.min_val.min()
+
+    def _update_hip(self, v: torch.Tensor) -> None:
+        """GPU tensors: this tensor's max / min from ``samq_minmax`` (init=1), then the running update
+        as f32 torch scalar ops on the device.  layer_wise reduces with ``MM_ALL`` directly: the
+        reference updates every channel's ``cur`` against the running scalar ``m`` and then takes
+        the max (min) over the channels, and ``cur -> m + sigma * (cur - m)`` is monotone
+        non-decreasing in ``cur`` (a subtraction, a product with sigma > 0 and a sum, each rounded
+        monotonically), so the max (min) of the updates is the update of the max (min): bit-identical."""
+        from . import ops
+        x2d, axis, _ = self._hip_view(v)
+        cur_max, cur_min = ops.minmax_update(x2d, axis)
+        if self.max_val is None:
+            self.max_val, self.min_val = cur_max, cur_min
+            return
+        if tuple(self.max_val.shape) != tuple(cur_max.shape) or not self.max_val.is_cuda:
+            raise ValueError(f"EmaObserver: running statistics of shape {tuple(self.max_val.shape)} "
+                             f"do not match this tensor's {tuple(cur_max.shape)}")
+        self.max_val = self.max_val + self.ema_sigma * (cur_max - self.max_val)
+        self.min_val = self.min_val + self.ema_sigma * (cur_min - self.min_val)
+
+    def get_quantization_params(self, *args, **kwargs):
+        return _uniform_params(self, self.max_val, self.min_val)
+
+
+def _quantile_ranks(n: int, q: float):
+    """Zero-based ranks ``(lo, hi)`` of the two order statistics that bracket quantile ``q`` of ``n``
+    values, as ``torch.quantile`` (n <= 2**24) or ``np.percentile`` on float32 data picks them."""
+    import numpy as np
+    if n <= 2 ** 24:
+        pos = torch.tensor(q, dtype=torch.float32) * (n - 1)
+        return int(pos.floor()), int(pos.ceil())
+    # numpy: q = true_divide(q * 100, float32(100)) is a float32; virtual index (n - 1) * q in float32
+    # (method "linear": _compute_virtual_index with alpha = beta = 1); _get_indexes takes floor and
+    # floor + 1, or the last element twice once the index reaches n - 1
+    vi = (n - 1) * np.true_divide(q * 100, np.float32(100))
+    if vi >= n - 1:
+        return n - 1, n - 1
+    lo = int(np.floor(vi))
+    return lo, lo + 1
+
+
+def quantile_from_order_stats(n: int, q: float, lo_val, hi_val) -> torch.Tensor:
+    """Quantile ``q`` of ``n`` float32 values from its two bracketing order statistics (the values at
+    ``_quantile_ranks(n, q)``), bit for bit what ``PercentileObserver`` gets from the libraries
+    (``percentile.py:27-39``): ``torch.quantile(v, q)`` for ``n <= 2**24`` -- ``q`` as f32, the
+    position ``q32 * (n - 1)`` in f32, ``torch.lerp`` between floor and ceil with the fractional
+    part -- and above that (where ``torch.quantile`` refuses the tensor) ``np.percentile(v, q * 100)``
+    on float32 input: ``q`` back to float32 by numpy's divide, float32 virtual index, gamma and
+    ``_lerp``.  Returns a 0-dim f32 CPU tensor."""
+    import numpy as np
+    lo_val, hi_val = float(lo_val), float(hi_val)
+    if n <= 2 ** 24:
+        pos = torch.tensor(q, dtype=torch.float32) * (n - 1)
+        weight = pos - pos.floor()
+        return torch.lerp(torch.tensor(lo_val, dtype=torch.float32), torch.tensor(hi_val, dtype=torch.float32),
+                          weight)
+    a, b = np.float32(lo_val), np.float32(hi_val)
+    vi = (n - 1) * np.true_divide(q * 100, np.float32(100))
+    gamma = np.float32(vi - np.floor(vi))                       # _get_gamma; dtype of the virtual index
+    with np.errstate(invalid="ignore", over="ignore"):
+        diff = np.subtract(b, a)                                # _lerp
+        out = np.add(a, diff * gamma)
+        if gamma >= 0.5:
+            out = np.subtract(b, diff * (1 - gamma))
+    return torch.tensor(float(out), dtype=torch.float32)
+
+
+class PercentileObserver(MinmaxObserver):
+    """``observer/percentile.py:9-71``: EMA of the ``percentile_alpha`` / ``1 - percentile_alpha``
+    quantiles of each calibration tensor (layer_wise only).  As in the reference, the constructor
+    arguments are accepted and the attributes are fixed at 0.01 / 0.99999."""
+
+    def __init__(self, module_type, bit_type, calibration_mode, percentile_sigma=0.01, percentile_alpha=0.99999,
+                 permute=True):
+        super().__init__(module_type, bit_type, calibration_mode, permute=permute)
+        self.percentile_sigma = 0.01
+        self.percentile_alpha = 0.99999
+
+    def update(self, v: torch.Tensor) -> None:
+        # channel-wise needs too much time (percentile.py:24-25)
+        assert self.calibration_mode == "layer_wise"
+        if v.is_cuda and self.use_hip:
+            cur_max, cur_min = self._quantiles_hip(v)
+        else:
+            flat = self.reshape_tensor(v).reshape(-1)
+            if flat.numel() <= 2 ** 24:
+                cur_max = torch.quantile(flat, self.percentile_alpha)
+                cur_min = torch.quantile(flat, 1.0 - self.percentile_alpha)
+            else:   # torch.quantile refuses the tensor: the reference's numpy fallback, on the host
+                import numpy as np
+                host = flat.cpu()
+                cur_max = torch.tensor(np.percentile(host, self.percentile_alpha * 100), dtype=torch.float32,
+                                       device=flat.device)
+                cur_min = torch.tensor(np.percentile(host, (1 - self.percentile_alpha) * 100), dtype=torch.float32,
+                                       device=flat.device)
+        self.max_val = cur_max if self.max_val is None else self.max_val + self.percentile_sigma * (cur_max - self.max_val)
+        self.min_val = cur_min if self.min_val is None else self.min_val + self.percentile_sigma * (cur_min - self.min_val)
+
+    def _quantiles_hip(self, v: torch.Tensor):
+        """GPU tensors: the four bracketing order statistics from one ``samq_order_stats`` call (a
+        quantile does not depend on the element order, so the tensor is read as it lies), finished
+        on the host by ``quantile_from_order_stats``.  The results go back to the device as f32
+        scalars, where the running update runs."""
+        from . import ops
+        v = v.detach()
+        if v.dtype not in (torch.float32, torch.float16):
+            v = v.float()
+        v = v.contiguous()
+        n = v.numel()
+        q_hi, q_lo = self.percentile_alpha, 1.0 - self.percentile_alpha
+        ranks = _quantile_ranks(n, q_hi) + _quantile_ranks(n, q_lo)
+        vals, flag = ops.order_stats(v.reshape(-1), ranks)
+        vals, nan = vals.cpu(), bool(flag.item())
+        if nan:   # torch.quantile and np.percentile both return NaN
+            cur_max = cur_min = torch.tensor(float("nan"), dtype=torch.float32)
+        else:
+            cur_max = quantile_from_order_stats(n, q_hi, vals[0], vals[1])
+            cur_min = quantile_from_order_stats(n, q_lo, vals[2], vals[3])
+        return cur_max.to(v.device), cur_min.to(v.device)
+
+    def get_quantization_params(self, *args, **kwargs):
+        return _uniform_params(self, self.max_val, self.min_val)
+
+
+OMSE_CANDIDATES = 90
+
+
+class OmseObserver(MinmaxObserver):
+    """``observer/omse.py:8-56``: minmax statistics; the quantisation range is then shrunk in 90 steps
+    of 1 % and the (scale, zero point) with the smallest mean squared fake-quant error wins."""
+
+    def _candidates(self):
+        """The reference's candidate loop head (``omse.py:39-44``), same scalar torch ops."""
+        qmax, qmin = self.bit_type.upper_bound, self.bit_type.lower_bound
+        out = []
+        for i in range(OMSE_CANDIDATES):
+            new_max = self.max_val * (1.0 - (i * 0.01))
+            new_min = self.min_val * (1.0 - (i * 0.01))
+            new_scale = (new_max - new_min) / float(qmax - qmin)
+            new_scale.clamp_(self.eps)
+            new_zero_point = qmin - torch.round(new_min / new_scale)
+            new_zero_point.clamp_(qmin, qmax)
+            out.append((new_max, new_min, new_scale, new_zero_point))
+        return out
+
+    def get_quantization_params(self, inputs):
+        qmax, qmin = self.bit_type.upper_bound, self.bit_type.lower_bound
+        if inputs.is_cuda and self.use_hip and self.calibration_mode == "layer_wise":
+            return self._params_hip(inputs)
+        best_score, best = 1e+10, None
+        for cand in self._candidates():
+            new_scale, new_zero_point = cand[2], cand[3]
+            inputs_q = ((inputs / new_scale + new_zero_point).round().clamp(qmin, qmax) - new_zero_point) * new_scale
+            score = (inputs - inputs_q).abs().pow(2.0).mean()   # lp_loss(p=2, reduction="all"), utils.py:9
+            if score < best_score:
+                best_score, best = score, cand
+        return self._pick(best)
+
+    def _pick(self, best):
+        if best is None:   # every score NaN or >= 1e10: the reference leaves its result unbound here
+            raise RuntimeError("OmseObserver: no candidate scored below 1e10 (NaN or inf in the calibration tensor?)")
+        self.max_val, self.min_val, scale, zero_point = best
+        return scale, zero_point
+
+    def _params_hip(self, inputs: torch.Tensor):
+        """GPU tensors, layer_wise: the 90 candidates are built on the host with the reference's
+        scalar ops (the CPU's correctly rounded division), one ``samq_omse_scores`` call reads the
+        tensor once and returns the 90 float64 sums of the f32 squared errors; the first strict
+        minimum of ``sum / numel`` in candidate order wins.  The exact sum replaces torch's f32
+        ``.mean()``, whose own rounding (up to ~3e-4 of the score) can order near-tied candidates
+        differently."""
+        from . import ops
+        dev = inputs.device
+        self.max_val, self.min_val = self.max_val.cpu(), self.min_val.cpu()
+        cands = self._candidates()
+        table = torch.tensor([[float(c[2]), float(c[3])] for c in cands], dtype=torch.float32)
+        x = inputs.detach()
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.float()
+        sums = ops.omse_scores(x.contiguous().reshape(-1), table.to(dev), self.bit_type.lower_bound,
+                               self.bit_type.upper_bound)
+        scores = (sums / x.numel()).cpu().tolist()
+        best_score, best = 1e+10, None
+        for cand, score in zip(cands, scores):
+            if score < best_score:
+                best_score, best = score, cand
+        scale, zero_point = self._pick(best)
+        self.max_val, self.min_val = self.max_val.to(dev), self.min_val.to(dev)
+        return scale.to(dev), zero_point.to(dev)
+
+
+OBSERVERS = {"minmax": MinmaxObserver, "ema": EmaObserver, "percentile": PercentileObserver, "omse": OmseObserver}
+
+
 def build_observer(observer_str, module_type, bit_type, calibration_mode, permute=True):
-    """``observer/build.py:17-19`` (minmax only)."""
-    if observer_str != "minmax":
-        raise NotImplementedError(f"observer {observer_str!r}: only minmax is supported")
-    return MinmaxObserver(module_type, bit_type, calibration_mode, permute=permute)
+    """``observer/build.py:8-19``: minmax, ema, percentile and omse (``ptf`` is not built)."""
+    if observer_str not in OBSERVERS:
+        raise NotImplementedError(f"observer {observer_str!r}: one of {sorted(OBSERVERS)} is supported")
+    return OBSERVERS[observer_str](module_type, bit_type, calibration_mode, permute=permute)
 
 
 class UniformQuantizer(nn.Module):
@@ -308,11 +554,17 @@ class QAct(nn.Module, _QFlags):
         self._init_q(quant, calibrate, last_calibrate, bit_type, calibration_mode, observer_str, quantizer_str,
                      "activation", permute=permute)
 
+    def _zero_point_is_zero(self) -> bool:
+        zp = self.quantizer.zero_point
+        return zp is None or not bool(zp.any())
+
     def forward(self, x):
         self._observe(x, x)
         if not self.quant:
             return x
-        if x.is_cuda and self.bit_type.signed and x.dtype == torch.float32 and self.quantizer.scale.numel() == 1:
+        # the HIP quantiser is the symmetric one: an omse-calibrated QAct (zero point != 0) takes the torch path
+        if (x.is_cuda and self.bit_type.signed and x.dtype == torch.float32 and self.quantizer.scale.numel() == 1
+                and self._zero_point_is_zero()):
             from . import ops
             return ops.quantize(x.contiguous(), float(self.quantizer.scale), fake=True)
         return self.quantizer(x)

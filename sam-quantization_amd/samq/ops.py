@@ -348,6 +348,47 @@ def minmax_update(x2d: torch.Tensor, axis: int, max_val: Optional[torch.Tensor] 
     return max_val, min_val
 
 
+def order_stats(x: torch.Tensor, ranks):
+    """Exact order statistics (``samq_order_stats``): the values at the zero-based ``ranks`` (1 to 4
+    Python ints) of the sorted flat f32 / f16 tensor ``x``.  Returns ``(values, nan_flag)``, an f32
+    tensor of ``len(ranks)`` values and a 0-dim int32 tensor (1 if ``x`` holds a NaN), both on the
+    device: nothing is synchronised here."""
+    _need_cuda(x)
+    assert x.is_contiguous() and x.dtype in (torch.float32, torch.float16) and x.numel() > 0
+    ranks = [int(r) for r in ranks]
+    n = x.numel()
+    assert 1 <= len(ranks) <= 4 and all(0 <= r < n for r in ranks), "order_stats: 1 to 4 ranks in [0, n)"
+    import ctypes
+    lib = _lib.load()
+    out = torch.empty(len(ranks), dtype=torch.float32, device=x.device)
+    flag = torch.empty((), dtype=torch.int32, device=x.device)
+    nws = lib.samq_order_stats_workspace(n, len(ranks))
+    ws = torch.empty((nws + 7) // 8, dtype=torch.int64, device=x.device)
+    host_ranks = (ctypes.c_int64 * len(ranks))(*ranks)
+    _lib.check(lib.samq_order_stats(_ptr(x), n, int(x.dtype == torch.float16), host_ranks, len(ranks), _ptr(out),
+                                    _ptr(flag), _ptr(ws), nws, _stream()), "order_stats")
+    return out, flag
+
+
+def omse_scores(x: torch.Tensor, cand: torch.Tensor, qmin: float, qmax: float) -> torch.Tensor:
+    """fq_vit ``OmseObserver`` candidate scores (``samq_omse_scores``): for each row (scale,
+    zero_point) of the f32 (ncand <= 96, 2) tensor ``cand``, the float64 sum over the flat f32 / f16
+    tensor ``x`` of ``(x - (clamp(round(x / s + zp), qmin, qmax) - zp) * s) ** 2``, every f32 step
+    rounded as torch's separate ops round it.  Returns a float64 (ncand,) tensor on the device."""
+    _need_cuda(x, cand)
+    assert x.is_contiguous() and x.dtype in (torch.float32, torch.float16) and x.numel() > 0
+    assert cand.dtype == torch.float32 and cand.is_contiguous() and cand.dim() == 2 and cand.shape[1] == 2
+    ncand = cand.shape[0]
+    assert 1 <= ncand <= 96
+    lib = _lib.load()
+    sums = torch.empty(ncand, dtype=torch.float64, device=x.device)
+    nws = lib.samq_omse_scores_workspace(x.numel(), ncand)
+    ws = torch.empty((nws + 7) // 8, dtype=torch.float64, device=x.device)
+    _lib.check(lib.samq_omse_scores(_ptr(x), x.numel(), int(x.dtype == torch.float16), _ptr(cand), ncand,
+                                    float(qmin), float(qmax), _ptr(sums), _ptr(ws), nws, _stream()), "omse_scores")
+    return sums
+
+
 def layernorm_q(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, in_scale: float = 0.0,
                 out_scale: float = 0.0, out_dtype: torch.dtype = torch.int8,
                 out: Optional[torch.Tensor] = None, rows_per_wave: int = 0,
