@@ -251,6 +251,59 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 
+// ---- fp32 residual epilogues (SAMQ_EPI_RESADD_F32: C += y, y staged through LDS per slice)
+// A wave's R-row x WN-column slice is res_j(R, WN) float4 per lane: float4 idx = j * 64 + lane
+// covers row idx / (WN / 4), columns 4 * (idx % (WN / 4)).  Written `*cp = *cp + v` per chunk, the
+// load of chunk j + 1 cannot pass the store of chunk j (same pointer) and vmcnt counts stores on
+// gfx950, so every chunk waits for the previous store's acknowledgement AND its own load: one
+// 16-byte access per lane in flight.  res_load reads the old residual of a whole slice into
+// registers instead; the epilogues issue it for the NEXT batch of slices before the stores of the
+// current one (each lane re-reads only addresses it alone writes, tiles are disjoint), so the
+// waits the compiler places are counted and never drain a younger store.  Rows at or past M are
+// clamped to row M - 1: read (and dropped), never stored -- no out-of-range row is touched.
+constexpr int res_j(int R, int WN) { return (R * (WN / 4) + 63) / 64; }
+template <int R, int WN>
+__device__ __forceinline__ void res_load(float4_t* xo, const void* C, int64_t ldc, int M, int srow0, int col_base,
+                                         int lane) {
+  constexpr int C4 = WN / 4;
+#pragma unroll
+  for (int j = 0; j < res_j(R, WN); ++j) {
+    int idx = j * 64 + lane;
+    idx = idx < R * C4 ? idx : R * C4 - 1;
+    int row = srow0 + idx / C4;
+    row = row < M ? row : M - 1;
+    xo[j] = *(const float4_t*)((const float*)C + (int64_t)row * ldc + col_base + 4 * (idx % C4));
+  }
+}
+// new residual x + v, computed where it is written: the empty asm keeps the add (and with it the
+// wait for x and the LDS read of v) out of the caller's divergent `row < M` store branch.  Sunk
+// into the branch, a wave that skips the store never waits for x, and the compiler then drains
+// the queue before the registers of x are loaded again -- the next batch's loads would wait for
+// this batch's.
+__device__ __forceinline__ float4_t res_add(float4_t x, float4_t v) {
+  float4_t s = x + v;
+  asm volatile("" : "+v"(s));
+  return s;
+}
+// An optional per-column fp16 operand (the bias; null = 0) read without a branch: the loads go
+// through p, or through the always-valid fallback where p is null (a global pointer, opaque to the
+// compiler so it neither folds them with the fallback's own loads nor moves them under a test of
+// p), and f32() clears the fallback's bits.  The callers issue all their scale / bias loads raw,
+// then convert behind ONE wait (`p ? (float)p[c] : 0` per column converts inside the branch: load,
+// wait, load, wait).
+struct HOpt {
+  const SAMQ_GLOBAL uint16_t* q;
+  uint32_t mask;
+  __device__ __forceinline__ HOpt(const _Float16* p, const _Float16* fallback)
+      : q((const SAMQ_GLOBAL uint16_t*)(p ? p : fallback)), mask(p ? 0xFFFFu : 0u) {
+    asm volatile("" : "+s"(q));
+  }
+  __device__ __forceinline__ uint32_t raw(int c) const { return q[c]; }
+  __device__ __forceinline__ float f32(uint32_t r) const {
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)(r & mask));
+  }
+};
+
 template <int N, typename F, int I = 0>
 __device__ __forceinline__ void static_for(F&& f) {   // f(integral_constant<int, 0..N-1>)
   if constexpr (I < N) {

@@ -96,18 +96,30 @@ __global__ void w8_repack_kernel(const int8_t* __restrict__ w, int8_t* __restric
 // factor is a_scale alone.
 // One 32-row slice i of the wave's accumulator tile (i8_epilogue runs all TM of them; the
 // tile ping-pong kernel spreads them over the other group's main loop).
-template <int TM, int TN, int WN, int EPI, bool ZPS = false, typename AccV = int16_t_v>
+// RESB (SAMQ_EPI_RESADD_F32, i8_epilogue): the old residual is read one slice ahead of the stores
+// (res_load, common.h): xcur = this slice's, loaded by the previous slice (the first by i8_epilogue);
+// xnext, where not null, receives slice i + 1's before this slice's stores.  RESB false: the
+// one-chunk-at-a-time read-modify-write (the tile ping-pong's scattered slices, A/B timing).
+template <int TM, int TN, int WN, int EPI, bool ZPS = false, typename AccV = int16_t_v, bool RESB = false>
 __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][TN], const int (&col)[TN],
                                                   const float* __restrict__ wscale, const float* __restrict__ bias,
                                                   const I8Epi& ep_args, float* ep, void* __restrict__ Cout,
                                                   int64_t ldc, int M, int row_base, int col_base, int lane,
-                                                  const int* ssum = nullptr, const int* zpv = nullptr) {
+                                                  const int* ssum = nullptr, const int* zpv = nullptr,
+                                                  const float4_t* xcur = nullptr, float4_t* xnext = nullptr,
+                                                  const float* scb = nullptr) {
+  static_assert(!RESB || EPI == SAMQ_EPI_RESADD_F32, "residual batches");
   const int hsel = lane >> 5;
   float csc[TN], cb[TN];
 #pragma unroll
   for (int t = 0; t < TN; ++t) {
-    csc[t] = wscale ? ep_args.a_scale * wscale[col[t]] : ep_args.a_scale;
-    cb[t] = bias ? bias[col[t]] : 0.0f;
+    if constexpr (RESB) {   // scb: the factors and biases of this lane's columns, loaded once per tile by
+      csc[t] = scb[t];      // i8_epilogue (reloaded per slice, their waits would drain the residual loads)
+      cb[t] = scb[TN + t];
+    } else {
+      csc[t] = wscale ? ep_args.a_scale * wscale[col[t]] : ep_args.a_scale;
+      cb[t] = bias ? bias[col[t]] : 0.0f;
+    }
   }
   constexpr bool GELU = EPI == SAMQ_EPI_BIAS_GELU || EPI == SAMQ_EPI_Q8_GELU;
   const float inv_out = ep_args.out_scale > 0.f ? 1.0f / ep_args.out_scale : 0.f;   // q8_exact (common.h)
@@ -163,6 +175,9 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
         }
       }
     }
+    if constexpr (RESB) {   // the next slice's residual: in flight over this slice's staging and stores
+      if (xnext) res_load<32, WN>(xnext, Cout, ldc, M, row_base + (i + 1) * 32, col_base, lane);
+    }
     __builtin_amdgcn_s_waitcnt(0xC07F);
     if (EPI == SAMQ_EPI_RESADD_F32 || EPI == SAMQ_EPI_F32) {
       constexpr int C4 = WN / 4;
@@ -171,10 +186,11 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
         const int idx = j * 64 + lane;
         const int rl = idx / C4, c4 = idx % C4;
         const int row = row_base + i * 32 + rl;
-        const float4_t v = ((const float4_t*)ep)[idx];
+        float4_t v = ((const float4_t*)ep)[idx];
+        if constexpr (RESB) v = res_add(xcur[j], v);
         if (row < M) {
           float4_t* cp = (float4_t*)((float*)Cout + (int64_t)row * ldc + col_base + 4 * c4);
-          if (EPI == SAMQ_EPI_RESADD_F32) *cp = *cp + v; else *cp = v;
+          if (EPI == SAMQ_EPI_RESADD_F32 && !RESB) *cp = *cp + v; else *cp = v;
         }
       }
     } else if (EPI == SAMQ_EPI_BIAS || EPI == SAMQ_EPI_BIAS_GELU) {
@@ -277,16 +293,33 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
   }
 }
 
-template <int TM, int TN, int WN, int EPI, bool ZPS = false, typename AccV = int16_t_v>
+// RES_OLD (tuning build, A/B timing): the fp32 residual one 16-byte chunk at a time
+template <int TM, int TN, int WN, int EPI, bool ZPS = false, typename AccV = int16_t_v, bool RES_OLD = false>
 __device__ __forceinline__ void i8_epilogue(const AccV (&acc)[TM][TN], const int (&col)[TN],
                                             const float* __restrict__ wscale, const float* __restrict__ bias,
                                             const I8Epi& ep_args, float* ep, void* __restrict__ Cout, int64_t ldc,
                                             int M, int row_base, int col_base, int lane,
                                             const int* ssum = nullptr, const int* zpv = nullptr) {
+  if constexpr (EPI == SAMQ_EPI_RESADD_F32 && !RES_OLD) {
+    float4_t xo[2][res_j(32, WN)];   // the old residual of the current and the next slice
+    res_load<32, WN>(xo[0], Cout, ldc, M, row_base, col_base, lane);
+    float scb[2 * TN];
 #pragma unroll
-  for (int i = 0; i < TM; ++i)
-    i8_epilogue_slice<TM, TN, WN, EPI, ZPS, AccV>(i, acc, col, wscale, bias, ep_args, ep, Cout, ldc, M, row_base,
-                                                  col_base, lane, ssum, zpv);
+    for (int t = 0; t < TN; ++t) {
+      scb[t] = wscale ? ep_args.a_scale * wscale[col[t]] : ep_args.a_scale;
+      scb[TN + t] = bias ? bias[col[t]] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+      i8_epilogue_slice<TM, TN, WN, EPI, ZPS, AccV, true>(i, acc, col, wscale, bias, ep_args, ep, Cout, ldc, M,
+                                                          row_base, col_base, lane, ssum, zpv, xo[i & 1],
+                                                          i + 1 < TM ? xo[(i + 1) & 1] : nullptr, scb);
+  } else {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+      i8_epilogue_slice<TM, TN, WN, EPI, ZPS, AccV>(i, acc, col, wscale, bias, ep_args, ep, Cout, ldc, M, row_base,
+                                                    col_base, lane, ssum, zpv);
+  }
 }
 
 // ------------------------------------------------------------------ GEMM
@@ -657,6 +690,8 @@ void i8_gemm_pp2(const int8_t* __restrict__ A, int64_t lda, const char* __restri
   uint32_t kLo = 0x0F0F0F0Fu;
   asm volatile("" : "+v"(kLo));
   constexpr bool ZPS = (VAR & 8) != 0;
+  // VAR & 128 (tuning build, A/B timing): the fp32 residual epilogue one 16-byte chunk at a time
+  constexpr bool RES_OLD = (VAR & 128) != 0;
   // VAR & 64 (with ZPS): the row sums come from the producer of A (ep_args.rs_in), loaded once here
   // -- older than every LDS-DMA piece, so the ring's counted waits retire it on the way -- instead
   // of 8 v_dot4 + 2 LDS reads per wave and phase
@@ -794,12 +829,14 @@ void i8_gemm_pp2(const int8_t* __restrict__ A, int64_t lda, const char* __restri
     int zpv[TN];
 #pragma unroll
     for (int t = 0; t < TN; ++t) zpv[t] = -(int)(zpx[t] & 0xFFu);
-    i8_epilogue<TM, TN, WN, EPI, true>(acc, col, wscale, bias, ep_args, (float*)(smem + wave * EP_BYTES), Cout,
-                                       ldc, M, m0 + wm * WM, n0 + wn * WN, lane, s_lds + wm * WM, zpv);
+    i8_epilogue<TM, TN, WN, EPI, true, int16_t_v, RES_OLD>(acc, col, wscale, bias, ep_args,
+                                                           (float*)(smem + wave * EP_BYTES), Cout, ldc, M, m0 + wm * WM,
+                                                           n0 + wn * WN, lane, s_lds + wm * WM, zpv);
     return;
   }
-  i8_epilogue<TM, TN, WN, EPI>(acc, col, wscale, bias, ep_args, (float*)(smem + wave * EP_BYTES), Cout, ldc, M,
-                               m0 + wm * WM, n0 + wn * WN, lane);
+  i8_epilogue<TM, TN, WN, EPI, false, int16_t_v, RES_OLD>(acc, col, wscale, bias, ep_args,
+                                                          (float*)(smem + wave * EP_BYTES), Cout, ldc, M, m0 + wm * WM,
+                                                          n0 + wn * WN, lane);
 }
 
 // ------------------------------------------------------------------ W4A8 tile ping-pong GEMM (round 5)
@@ -1107,6 +1144,10 @@ static int launch_i8_cfg(const I8Args& a, int cfg, hipStream_t st) {
     case 99:   // tile ping-pong: one group's epilogue under the other group's main loop (correct, slower)
       if constexpr (BF == BF_W4) return launch_i8_tpp<EPI>(a, st);
       else return fail(SAMQ_ERR_INVALID, "i8_gemm: cfg 99 is a W4 kernel");
+    case 98:   // A/B: cfg 86 with the fp32 residual read-modify-written one 16-byte chunk at a time
+      if constexpr (BF == BF_W4)
+        return a.ep.rs_in ? launch_i8_pp2<EPI, 3, 2, 8 | 64 | 128>(a, st) : launch_i8_pp2<EPI, 3, 2, 8 | 128>(a, st);
+      return fail(SAMQ_ERR_INVALID, "i8_gemm: W4 only");
     case 94:   // timing-only: cfg 86 without its epilogue
       if constexpr (BF == BF_W4) return launch_i8_pp2<EPI, 3, 2, 8 | 32>(a, st);
       return fail(SAMQ_ERR_INVALID, "i8_gemm: W4 only");
@@ -1140,7 +1181,7 @@ static int launch_i8_cfg(const I8Args& a, int cfg, hipStream_t st) {
 }
 
 static int i8_cfg_bn(int cfg) {
-  switch (cfg) { case 81: case 82: case 85: case 86: case 93: case 94: case 95: case 96: case 97: return 256; case 83: case 88: case 90: case 99: case 180: case 182: return 128; case 84: case 87: case 89: case 91: case 181: return 64;
+  switch (cfg) { case 81: case 82: case 85: case 86: case 93: case 94: case 95: case 96: case 97: case 98: return 256; case 83: case 88: case 90: case 99: case 180: case 182: return 128; case 84: case 87: case 89: case 91: case 181: return 64;
     case 92: return 32; default: return 0; }
 }
 

@@ -264,8 +264,21 @@ void w4a16_gemm_kernel(const _Float16* __restrict__ A, int64_t lda,
     csc[t] = GROUPED ? 1.0f : (float)scales[col[t]];
     cb[t] = bias ? (float)bias[col[t]] : 0.0f;
   }
+  // fp32 residual: the old values of a 32-row tile are all read before its first store (rows past
+  // M clamped: read, never stored; common.h res_load)
+  constexpr bool RES = EPI == SAMQ_EPI_RESADD_F32;
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
+    float xo[RES ? 16 : 1][TN];
+    if constexpr (RES) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
+        row = row < M ? row : M - 1;
+#pragma unroll
+        for (int t = 0; t < TN; ++t) xo[r][t] = ((const float*)Cout)[(int64_t)row * ldc + col[t]];
+      }
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
@@ -276,7 +289,7 @@ void w4a16_gemm_kernel(const _Float16* __restrict__ A, int64_t lda,
         if (EPI == SAMQ_EPI_BIAS_GELU) v = gelu_erf(v);
         if (EPI == SAMQ_EPI_RESADD_F32) {
           float* cp = (float*)Cout + (int64_t)row * ldc + col[t];
-          *cp = *cp + v;
+          *cp = xo[RES ? r : 0][t] + v;
         } else if (EPI == SAMQ_EPI_F32) {
           ((float*)Cout)[(int64_t)row * ldc + col[t]] = v;
         } else {
@@ -473,14 +486,24 @@ __device__ __forceinline__ half8_t lnf_out8(float4_t v0, float4_t v1, float2_t r
 // of 16-row tile i, 32-column block t, half h holds rows 16i + 4g + r of column 32t + 16h + ql;
 // staged per 16-row tile with a padded pitch (WN + 4 floats: the four lane groups' rows land
 // on different banks).
-template <int TM16, int TN, int EPI>
+// RES (SAMQ_EPI_RESADD_F32): the old residual is read a batch of RES_NB16 slices ahead (res_load,
+// common.h).  xpre = the first batch, loaded by the caller before the epilogue's barrier.
+constexpr int RES_NB16 = 2;
+template <int TM16, int TN, int EPI, bool RES = false>
 __device__ __forceinline__ void pp_epilogue16(const float4_t (&acc)[TM16][TN][2], const float (&csc)[TN][2],
                                               const float (&cb)[TN][2], char* ep_bytes, void* Cout, int64_t ldc,
                                               int M, int row_base, int col_base, int lane,
                                               const LnfArgs& L = LnfArgs{}, int N = 0,
-                                              const float2_t* rowinfo = nullptr) {
+                                              const float2_t* rowinfo = nullptr, const float4_t* xpre = nullptr) {
   constexpr int WN = TN * 32, EP_ROWS = 16, PITCH = WN + 4;
   static_assert(!(lnf_producer(EPI) || lnf_consumer(EPI)) || WN == 64, "LN fold: 64-column wave tiles");
+  static_assert(!RES || (EPI == SAMQ_EPI_RESADD_F32 && TM16 % RES_NB16 == 0), "residual batches");
+  constexpr int RJ = res_j(EP_ROWS, WN), RX = RES ? RES_NB16 * RJ : 1;
+  float4_t xo[2][RX];   // RES: the old residual of the current and the next batch of slices
+  if constexpr (RES) {
+#pragma unroll
+    for (int k = 0; k < RX; ++k) xo[0][k] = xpre[k];
+  }
   float* ep = (float*)ep_bytes;
   const int ql = lane & 15, g = lane >> 4;
   float gw8[8], bb8[8];   // LNF consumer: this lane's 8 columns (fixed over the slices)
@@ -504,6 +527,14 @@ __device__ __forceinline__ void pp_epilogue16(const float4_t (&acc)[TM16][TN][2]
           if (EPI == SAMQ_EPI_BIAS_GELU) v = gelu_fast(v);
           ep[(4 * g + r) * PITCH + 32 * t + 16 * h + ql] = v;
         }
+    if constexpr (RES) {   // the next batch's residual: in flight over this batch's staging and stores
+      if (i % RES_NB16 == 0 && i + RES_NB16 < TM16) {
+#pragma unroll
+        for (int b = 0; b < RES_NB16; ++b)
+          res_load<EP_ROWS, WN>(&xo[(i / RES_NB16 + 1) & 1][b * RJ], Cout, ldc, M, row_base + (i + RES_NB16 + b) * 16,
+                                col_base, lane);
+      }
+    }
     __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the slice is in LDS (same wave reads it)
     const int srow0 = row_base + i * 16;
     if (lnf_producer(EPI)) {
@@ -516,10 +547,11 @@ __device__ __forceinline__ void pp_epilogue16(const float4_t (&acc)[TM16][TN][2]
         if (idx < EP_ROWS * C4) {
           const int rl = idx / C4, c4 = idx % C4;
           const int row = srow0 + rl;
-          const float4_t v = *(const float4_t*)(ep + rl * PITCH + 4 * c4);
+          float4_t v = *(const float4_t*)(ep + rl * PITCH + 4 * c4);
+          if constexpr (RES) v = res_add(xo[(i / RES_NB16) & 1][(i % RES_NB16) * RJ + j], v);
           if (row < M) {
             float4_t* cp = (float4_t*)((float*)Cout + (int64_t)row * ldc + col_base + 4 * c4);
-            if (EPI == SAMQ_EPI_RESADD_F32) *cp = *cp + v; else *cp = v;
+            if (EPI == SAMQ_EPI_RESADD_F32 && !RES) *cp = *cp + v; else *cp = v;
           }
         }
       }
@@ -720,15 +752,31 @@ void w4a16_gemm_v3(const _Float16* __restrict__ A, int64_t lda, const u32x4* __r
   // global traffic is row-contiguous 16-byte vectors (f16: 8 columns / lane; f32 residual:
   // 4 columns / lane read-modify-write) instead of one 2- or 4-byte access per accumulator.
   float csc[TN], cb[TN];
+  {
+    const HOpt bo(bias, scales);
+    _Float16 rs[TN];           // one batch of raw loads behind a single wait (bias null: 0)
+    uint32_t rb[TN];
 #pragma unroll
-  for (int t = 0; t < TN; ++t) {
-    csc[t] = GROUPED ? 1.0f : (float)scales[col[t]];
-    cb[t] = bias ? (float)bias[col[t]] : 0.0f;
+    for (int t = 0; t < TN; ++t) {
+      rs[t] = GROUPED ? (_Float16)1.0f : scales[col[t]];
+      rb[t] = bo.raw(col[t]);
+    }
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+      csc[t] = GROUPED ? 1.0f : (float)rs[t];
+      cb[t] = bo.f32(rb[t]);
+    }
   }
-  __syncthreads();                                      // every wave is done with the ring
-  float* ep = (float*)(smem + wave * EP_BYTES);
   const int row_base = m0 + wm * WM;
   const int col_base = n0 + wn * WN;
+  // fp32 residual: the old values a 32-row slice ahead of the stores (res_load, common.h), the
+  // first slice's before the barrier
+  constexpr bool RES = EPI == SAMQ_EPI_RESADD_F32;
+  constexpr int RJ = RES ? res_j(32, WN) : 1;
+  float4_t xo[2][RJ];
+  if constexpr (RES) res_load<32, WN>(xo[0], Cout, ldc, M, row_base, col_base, lane);
+  __syncthreads();                                      // every wave is done with the ring
+  float* ep = (float*)(smem + wave * EP_BYTES);
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -741,6 +789,9 @@ void w4a16_gemm_v3(const _Float16* __restrict__ A, int64_t lda, const u32x4* __r
         ep[rl * WN + t * 32 + (lane & 31)] = v;
       }
     }
+    if constexpr (RES) {
+      if (i + 1 < TM) res_load<32, WN>(xo[(i + 1) & 1], Cout, ldc, M, row_base + (i + 1) * 32, col_base, lane);
+    }
     __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the slice is in LDS (same wave reads it)
     if (EPI == SAMQ_EPI_RESADD_F32 || EPI == SAMQ_EPI_F32) {
       constexpr int C4 = WN / 4;                        // float4 per slice row
@@ -749,11 +800,9 @@ void w4a16_gemm_v3(const _Float16* __restrict__ A, int64_t lda, const u32x4* __r
         const int idx = j * 64 + lane;
         const int rl = idx / C4, c4 = idx % C4;
         const int row = row_base + i * 32 + rl;
-        const float4_t v = ((const float4_t*)ep)[idx];
-        if (row < M) {
-          float4_t* cp = (float4_t*)((float*)Cout + (int64_t)row * ldc + col_base + 4 * c4);
-          if (EPI == SAMQ_EPI_RESADD_F32) *cp = *cp + v; else *cp = v;
-        }
+        float4_t v = ((const float4_t*)ep)[idx];
+        if constexpr (RES) v = res_add(xo[i & 1][j], v);
+        if (row < M) *(float4_t*)((float*)Cout + (int64_t)row * ldc + col_base + 4 * c4) = v;
       }
     } else {
       constexpr int C8 = WN / 8;                        // 8-column chunks per slice row
@@ -946,6 +995,20 @@ void w4a16_gemm_v4(const _Float16* __restrict__ A, int64_t lda, const u32x4* __r
       const int c = col[t][h];
       const float cs = GROUPED ? 1.0f : (float)scales[c];
       const float cb = bias ? (float)bias[c] : 0.0f;
+      // fp32 residual: this column's old values all read before its first store (rows past M
+      // clamped: read, never stored; common.h res_load)
+      constexpr bool RES = EPI == SAMQ_EPI_RESADD_F32;
+      float xo[RES ? TM : 1][4];
+      if constexpr (RES) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            int row = m0 + wm * WM + i * 16 + 4 * g + r;
+            row = row < M ? row : M - 1;
+            xo[i][r] = ((const float*)Cout)[(int64_t)row * ldc + c];
+          }
+      }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -956,7 +1019,7 @@ void w4a16_gemm_v4(const _Float16* __restrict__ A, int64_t lda, const u32x4* __r
           if (EPI == SAMQ_EPI_BIAS_GELU) v = gelu_fast(v);
           if (EPI == SAMQ_EPI_RESADD_F32) {
             float* cp = (float*)Cout + (int64_t)row * ldc + c;
-            *cp = *cp + v;
+            *cp = xo[RES ? i : 0][r] + v;
           } else if (EPI == SAMQ_EPI_F32) {
             ((float*)Cout)[(int64_t)row * ldc + c] = v;
           } else {
@@ -969,14 +1032,23 @@ void w4a16_gemm_v4(const _Float16* __restrict__ A, int64_t lda, const u32x4* __r
 // y = acc * s[n] + b[n] (-> GELU / residual add), staged through LDS in EP_ROWS-row slices per
 // wave so the global traffic is row-contiguous 16-byte vectors (v3's epilogue)
 // EVAR (tuning build, timing-only): 1 = f16 outputs staged but not stored, 2 = no scale / bias / GELU
-template <int TM, int TN, int EP_ROWS, int EPI, int EVAR = 0>
+// RES (SAMQ_EPI_RESADD_F32): the old residual is read one slice ahead of the stores (res_load,
+// common.h); xpre = the first slice's, loaded by the caller before the epilogue's barrier
+template <int TM, int TN, int EP_ROWS, int EPI, int EVAR = 0, bool RES = false>
 __device__ __forceinline__ void pp_epilogue(const float16_t (&acc)[TM][TN], const float (&csc)[TN],
                                             const float (&cb)[TN], char* ep_bytes, void* Cout, int64_t ldc,
                                             int M, int row_base, int col_base, int lane,
                                             const LnfArgs& L = LnfArgs{}, int N = 0,
-                                            const float2_t* rowinfo = nullptr) {
+                                            const float2_t* rowinfo = nullptr, const float4_t* xpre = nullptr) {
   constexpr int WN = TN * 32;
   constexpr int NSL = 32 / EP_ROWS;
+  static_assert(!RES || EPI == SAMQ_EPI_RESADD_F32, "residual batches");
+  constexpr int RJ = RES ? res_j(EP_ROWS, WN) : 1;
+  float4_t xo[2][RJ];   // RES: the old residual of the current and the next slice
+  if constexpr (RES) {
+#pragma unroll
+    for (int k = 0; k < RJ; ++k) xo[0][k] = xpre[k];
+  }
   static_assert(!(lnf_producer(EPI) || lnf_consumer(EPI)) || WN == 64, "LN fold: 64-column wave tiles");
   float* ep = (float*)ep_bytes;
   const int hsel = lane >> 5;
@@ -1043,8 +1115,12 @@ __device__ __forceinline__ void pp_epilogue(const float16_t (&acc)[TM][TN], cons
           ep[(rl + 1) * WN + cs] = v.y;
         }
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the slice is in LDS (same wave reads it)
       const int srow0 = row_base + i * 32 + sl * EP_ROWS;
+      const int sn = i * NSL + sl;   // slice number
+      if constexpr (RES) {   // the next slice's residual: in flight over this slice's staging and stores
+        if (sn + 1 < TM * NSL) res_load<EP_ROWS, WN>(xo[(sn + 1) & 1], Cout, ldc, M, srow0 + EP_ROWS, col_base, lane);
+      }
+      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the slice is in LDS (same wave reads it)
       if (lnf_producer(EPI)) {
         lnf_produce_slice<EP_ROWS, WN>(L, ep, (float*)Cout, ldc, N, M, srow0, col_base, lane);
       } else if (lnf_consumer(EPI)) {
@@ -1071,10 +1147,11 @@ __device__ __forceinline__ void pp_epilogue(const float16_t (&acc)[TM][TN], cons
           if (idx < EP_ROWS * C4) {
             const int rl = idx / C4, c4 = idx % C4;
             const int row = srow0 + rl;
-            const float4_t v = ((const float4_t*)ep)[idx];
+            float4_t v = ((const float4_t*)ep)[idx];
+            if constexpr (RES) v = res_add(xo[sn & 1][j], v);
             if (row < M) {
               float4_t* cp = (float4_t*)((float*)Cout + (int64_t)row * ldc + col_base + 4 * c4);
-              if (EPI == SAMQ_EPI_RESADD_F32) *cp = *cp + v; else *cp = v;
+              if (EPI == SAMQ_EPI_RESADD_F32 && !RES) *cp = *cp + v; else *cp = v;
             }
           }
         }
@@ -1165,9 +1242,17 @@ __device__ __forceinline__ void pp_epilogue_f16t(const float16_t (&acc)[TM][TN],
 // row per register group and stores them straight from registers (G = 4: 8 bytes of fp16 or 16
 // bytes of fp32, a 16-byte read-modify-write for the residual) -- no LDS staging round trip
 // (ds_write_b32 per element + ds_read_b128 + waits in pp_epilogue).  v[q] = acc[q] * s[n] + b[n].
+// fp32 residual: xo = the chunk's old values, read by te_res4 for all of a column group's rows
+// before the group's first store (rows past M clamped: read, never stored; common.h res_load)
+template <int EPI>
+__device__ __forceinline__ float4_t te_res4(const void* Cout, int64_t ldc, int M, int row, int col) {
+  if constexpr (EPI != SAMQ_EPI_RESADD_F32) return float4_t{0.f, 0.f, 0.f, 0.f};
+  row = row < M ? row : M - 1;
+  return *(const float4_t*)((const float*)Cout + (int64_t)row * ldc + col);
+}
 template <int EPI>
 __device__ __forceinline__ void te_store4(const float4_t& acc, const float4_t& sc, const float4_t& bi, void* Cout,
-                                          int64_t ldc, int M, int row, int col) {
+                                          int64_t ldc, int M, int row, int col, float4_t xo) {
   if (row >= M) return;
   float2_t v0 = __builtin_elementwise_fma((float2_t){acc[0], acc[1]}, (float2_t){sc[0], sc[1]}, (float2_t){bi[0], bi[1]});
   float2_t v1 = __builtin_elementwise_fma((float2_t){acc[2], acc[3]}, (float2_t){sc[2], sc[3]}, (float2_t){bi[2], bi[3]});
@@ -1178,7 +1263,7 @@ __device__ __forceinline__ void te_store4(const float4_t& acc, const float4_t& s
   if (EPI == SAMQ_EPI_RESADD_F32 || EPI == SAMQ_EPI_F32) {
     float4_t* cp = (float4_t*)((float*)Cout + (int64_t)row * ldc + col);
     const float4_t v = {v0.x, v0.y, v1.x, v1.y};
-    if (EPI == SAMQ_EPI_RESADD_F32) *cp = *cp + v; else *cp = v;
+    if (EPI == SAMQ_EPI_RESADD_F32) *cp = xo + v; else *cp = v;
   } else {
     const half2_t h0 = __builtin_convertvector(v0, half2_t), h1 = __builtin_convertvector(v1, half2_t);
     *(half4_t*)((_Float16*)Cout + (int64_t)row * ldc + col) = half4_t{h0.x, h0.y, h1.x, h1.y};
@@ -1808,9 +1893,12 @@ void pp2_tile(const _Float16* __restrict__ A, int64_t lda, const u32x4* __restri
         const half4_t b4 = bias ? *(const half4_t*)(bias + c) : half4_t{0, 0, 0, 0};
         const float4_t sc = {(float)s4[0], (float)s4[1], (float)s4[2], (float)s4[3]};
         const float4_t bi = {(float)b4[0], (float)b4[1], (float)b4[2], (float)b4[3]};
+        float4_t xo[2 * TM];
+#pragma unroll
+        for (int i = 0; i < 2 * TM; ++i) xo[i] = te_res4<EPI>(Cout, ldc, M, m0 + wm * WM + 16 * i + ql, c);
 #pragma unroll
         for (int i = 0; i < 2 * TM; ++i)
-          te_store4<EPI>(acc16[i][t][h], sc, bi, Cout, ldc, M, m0 + wm * WM + 16 * i + ql, c);
+          te_store4<EPI>(acc16[i][t][h], sc, bi, Cout, ldc, M, m0 + wm * WM + 16 * i + ql, c, xo[i]);
       }
     return;
   }
@@ -1832,39 +1920,100 @@ void pp2_tile(const _Float16* __restrict__ A, int64_t lda, const u32x4* __restri
         const half4_t b4 = bias ? *(const half4_t*)(bias + c) : half4_t{0, 0, 0, 0};
         const float4_t sc = {(float)s4[0], (float)s4[1], (float)s4[2], (float)s4[3]};
         const float4_t bi = {(float)b4[0], (float)b4[1], (float)b4[2], (float)b4[3]};
+        float4_t xo[TM];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) xo[i] = te_res4<EPI>(Cout, ldc, M, m0 + wm * WM + 32 * i + (lane & 31), c);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           const float4_t a = {acc[i][t][4 * j], acc[i][t][4 * j + 1], acc[i][t][4 * j + 2], acc[i][t][4 * j + 3]};
-          te_store4<EPI>(a, sc, bi, Cout, ldc, M, m0 + wm * WM + 32 * i + (lane & 31), c);
+          te_store4<EPI>(a, sc, bi, Cout, ldc, M, m0 + wm * WM + 32 * i + (lane & 31), c, xo[i]);
         }
       }
     return;
   }
+  // fp32 residual (SAMQ_EPI_RESADD_F32): the old values are read a batch of slices ahead of the
+  // stores (res_load, common.h), the first batch here -- behind the scale / bias loads, which
+  // return first, and before the barrier, so it is in flight over both.  VAR & (1 << 24) (tuning
+  // build, A/B timing): the one-chunk-at-a-time read-modify-write and per-column operand loads.
+  constexpr bool RES_OLD = (VAR & (1 << 24)) != 0;
+  constexpr bool RES = EPI == SAMQ_EPI_RESADD_F32 && !RES_OLD;
+  constexpr int RES_R = M16 ? 16 : EP_ROWS, RES_NB = M16 ? RES_NB16 : 1;
+  constexpr int RES_J = res_j(RES_R, WN), RES_NX = RES ? RES_NB * RES_J : 1;
+  float4_t xpre[RES_NX];
+  auto res_first = [&]() {
+    if constexpr (RES) {
+#pragma unroll
+      for (int b = 0; b < RES_NB; ++b)
+        res_load<RES_R, WN>(xpre + b * RES_J, Cout, ldc, M, m0 + wm * WM + b * RES_R, n0 + wn * WN, lane);
+    }
+  };
   if constexpr (M16) {
     float csc16[TN][2], cb16[TN][2];
+    if constexpr (EARLY_EP || GR || RES_OLD) {
 #pragma unroll
-    for (int t = 0; t < TN; ++t)
+      for (int t = 0; t < TN; ++t)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int c = n0 + wn * WN + 32 * t + 16 * h + ql;
-        csc16[t][h] = EARLY_EP ? (float)esc[EARLY_EP ? 2 * t + h : 0] : GR ? 1.0f : (float)scales[c];
-        cb16[t][h] = EARLY_EP ? (float)ebi[EARLY_EP ? 2 * t + h : 0] : bias ? (float)bias[c] : 0.0f;
-      }
+        for (int h = 0; h < 2; ++h) {
+          const int c = n0 + wn * WN + 32 * t + 16 * h + ql;
+          csc16[t][h] = EARLY_EP ? (float)esc[EARLY_EP ? 2 * t + h : 0] : GR ? 1.0f : (float)scales[c];
+          cb16[t][h] = EARLY_EP ? (float)ebi[EARLY_EP ? 2 * t + h : 0] : bias ? (float)bias[c] : 0.0f;
+        }
+      res_first();
+    } else {
+      // this lane's scales and biases as one batch of raw loads behind a single wait (bias null: 0)
+      const HOpt bo(bias, scales);
+      _Float16 rs[TN][2];
+      uint32_t rb[TN][2];
+#pragma unroll
+      for (int t = 0; t < TN; ++t)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int c = n0 + wn * WN + 32 * t + 16 * h + ql;
+          rs[t][h] = scales[c];
+          rb[t][h] = bo.raw(c);
+        }
+      res_first();
+#pragma unroll
+      for (int t = 0; t < TN; ++t)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          csc16[t][h] = (float)rs[t][h];
+          cb16[t][h] = bo.f32(rb[t][h]);
+        }
+    }
     __syncthreads();
     float2_t* rowinfo = (float2_t*)(smem + NW * EP_BYTES) + wm * WM;
     lnf.bias = bias;
     if constexpr (lnf_consumer(EPI))
       lnf_rowinfo_wg<BM, NW>(lnf, (float2_t*)(smem + NW * EP_BYTES), smem + NW * EP_BYTES + RI_BYTES, M, m0, n0 == 0,
                              wave, lane);
-    pp_epilogue16<2 * TM, TN, EPI>(acc16, csc16, cb16, smem + wave * EP_BYTES, Cout, ldc, M, m0 + wm * WM,
-                                   n0 + wn * WN, lane, lnf, N, rowinfo);
+    pp_epilogue16<2 * TM, TN, EPI, RES>(acc16, csc16, cb16, smem + wave * EP_BYTES, Cout, ldc, M, m0 + wm * WM,
+                                        n0 + wn * WN, lane, lnf, N, rowinfo, xpre);
     return;
   }
   float csc[TN], cb[TN];
+  if constexpr (EARLY_EP || GR || RES_OLD) {
 #pragma unroll
-  for (int t = 0; t < TN; ++t) {
-    csc[t] = EARLY_EP ? (float)esc[EARLY_EP ? t : 0] : GR ? 1.0f : (float)scales[col[t]];
-    cb[t] = EARLY_EP ? (float)ebi[EARLY_EP ? t : 0] : bias ? (float)bias[col[t]] : 0.0f;
+    for (int t = 0; t < TN; ++t) {
+      csc[t] = EARLY_EP ? (float)esc[EARLY_EP ? t : 0] : GR ? 1.0f : (float)scales[col[t]];
+      cb[t] = EARLY_EP ? (float)ebi[EARLY_EP ? t : 0] : bias ? (float)bias[col[t]] : 0.0f;
+    }
+    res_first();
+  } else {
+    const HOpt bo(bias, scales);
+    _Float16 rs[TN];           // one batch of raw loads behind a single wait (bias null: 0)
+    uint32_t rb[TN];
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+      rs[t] = scales[col[t]];
+      rb[t] = bo.raw(col[t]);
+    }
+    res_first();
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+      csc[t] = (float)rs[t];
+      cb[t] = bo.f32(rb[t]);
+    }
   }
   __syncthreads();
   float2_t* rowinfo = (float2_t*)(smem + NW * EP_BYTES) + wm * WM;
@@ -1878,8 +2027,8 @@ void pp2_tile(const _Float16* __restrict__ A, int64_t lda, const u32x4* __restri
     pp_epilogue_f16t<TM, TN, EPI>(acc, csc, cb, smem + wave * EP_BYTES, Cout, ldc, M, m0 + wm * WM, n0 + wn * WN, lane);
     return;
   }
-  pp_epilogue<TM, TN, EP_ROWS, EPI, (VAR >> 17) & 3>(acc, csc, cb, smem + wave * EP_BYTES, Cout, ldc, M, m0 + wm * WM,
-                                                     n0 + wn * WN, lane, lnf, N, rowinfo);
+  pp_epilogue<TM, TN, EP_ROWS, EPI, (VAR >> 17) & 3, RES>(acc, csc, cb, smem + wave * EP_BYTES, Cout, ldc, M,
+                                                          m0 + wm * WM, n0 + wn * WN, lane, lnf, N, rowinfo, xpre);
 }
 
 // The ping-pong GEMM kernel: one tile per workgroup, or (VAR & (1 << 20), persistent) a grid of at
@@ -2094,6 +2243,10 @@ static int launch_epi(const GemmArgs& a, int cfg, hipStream_t st) {
       case 105: return launch_pp2<2, 4, 2, 2, 4, 3, EPI, 4096 | (1 << 17)>(a, st);
       case 106: return launch_pp2<2, 4, 2, 2, 4, 3, EPI, 4096 | (2 << 17)>(a, st);
       case 103: return launch_pp2<2, 4, 2, 2, 4, 3, EPI, 16 | 4096 | 32768>(a, st);
+      // A/B: cfg 57 / 64 with the fp32 residual read-modify-written one 16-byte chunk at a time and
+      // the scale / bias loads one per wait (the form before the batched residual epilogue)
+      case 117: return launch_pp2<2, 4, 2, 2, 4, 3, EPI, 4096 | (1 << 24)>(a, st);
+      case 118: return launch_pp2<2, 4, 2, 2, 4, 3, EPI, 16 | 4096 | (1 << 24)>(a, st);
       case 71: return launch_pp2<2, 4, 2, 2, 4, 3, EPI, 2>(a, st);   // timing-only: cfg 57 without MFMA
       case 72: return launch_pp2<2, 4, 2, 2, 4, 3, EPI, 3>(a, st);   // timing-only: neither
       case 73: {   // timing experiment: cfg 57 with per-segment s_memtime stamps (synchronous)
@@ -2189,7 +2342,7 @@ static int cfg_bn(int cfg) {
                  case 74: case 75: case 76: case 77: case 78: case 79: return 256;
                  case 90: case 91: case 92: case 93: case 94: case 95: case 96: return 256;
                  case 97: case 98: return 512;
-                 case 100: case 101: case 102: case 103: case 104: case 105: case 106: case 107: case 108: case 109: case 110: case 111: case 112: case 113: case 114: case 115: case 116: return 256;
+                 case 100: case 101: case 102: case 103: case 104: case 105: case 106: case 107: case 108: case 109: case 110: case 111: case 112: case 113: case 114: case 115: case 116: case 117: case 118: return 256;
                  default: return 0; }
 }
 
