@@ -429,7 +429,8 @@ __device__ __forceinline__ void lnf_produce_slice(const LnfArgs& L, const float*
 // consumer: (delta, rstd) of the workgroup's BM rows into LDS (rowinfo[BM]), mu += delta by the
 // workgroups of column tile 0.  The rows' partial sums (BM x nblk float2, contiguous) arrive by
 // LDS-DMA (1 KiB pieces dealt over the NW waves, one wait), then one lane per row adds its nblk
-// pairs in block order from LDS (the order of the standalone reduction: same bits).
+// pairs in block order from LDS (the order of the standalone reduction: same bits).  No read
+// leaves stats[0 .. M * nblk * 2).
 template <int BM, int NW>
 __device__ __forceinline__ void lnf_rowinfo_wg(const LnfArgs& L, float2_t* rowinfo, char* sbuf, int M, int row_base,
                                                bool col0, int wave, int lane) {
@@ -437,11 +438,20 @@ __device__ __forceinline__ void lnf_rowinfo_wg(const LnfArgs& L, float2_t* rowin
   const int nfl = 2 * L.nblk;                                 // floats per row
   const int npieces = BM * nfl / 256;                         // 1 KiB pieces (BM * nblk * 8 / 1024)
   const float* base = L.stats + (int64_t)row_base * nfl;
-  const int64_t lim = (int64_t)(M - row_base) * nfl - 4;      // last in-bounds 16-byte chunk
-  for (int pc = wave; pc < npieces; pc += NW) {
-    int64_t off = (int64_t)(pc * 64 + lane) * 4;
-    off = off <= lim ? off : lim;
-    __builtin_amdgcn_global_load_lds((const SAMQ_GLOBAL void*)(base + off), (SAMQ_LDS void*)(sbuf + pc * 1024), 16, 0, 0);
+  const int64_t nvalid = (int64_t)(M - row_base) * nfl;       // floats of the rows < M, from base
+  const int64_t lim = nvalid - 4;                             // last in-bounds 16-byte chunk
+  // A chunk past lim is clamped to it, which leaves the slots of rows >= M with stale pairs (never
+  // used).  Where the valid rows end 8 bytes past a 16-byte boundary (rows left and nblk both odd)
+  // the chunk holding the last row's last pair is clamped back by one pair as well: that one pair
+  // is read from global memory by its row's lane below.  lim < 0 (M = 1, nblk = 1: 8 bytes of
+  // stats in all) has no in-bounds chunk: nothing is staged.
+  const int tail_rl = (nvalid & 2) != 0 && M - row_base <= BM ? M - row_base - 1 : -1;
+  if (lim >= 0) {
+    for (int pc = wave; pc < npieces; pc += NW) {
+      int64_t off = (int64_t)(pc * 64 + lane) * 4;
+      off = off <= lim ? off : lim;
+      __builtin_amdgcn_global_load_lds((const SAMQ_GLOBAL void*)(base + off), (SAMQ_LDS void*)(sbuf + pc * 1024), 16, 0, 0);
+    }
   }
   vm_wait<0>();
   __syncthreads();
@@ -453,11 +463,15 @@ __device__ __forceinline__ void lnf_rowinfo_wg(const LnfArgs& L, float2_t* rowin
     if (q * 64 + lane < RPW) {
       const float2_t* sp = (const float2_t*)(sbuf + rl * nfl * 4);
       float s1 = 0.f, s2 = 0.f;
-      for (int b = 0; b < L.nblk; ++b) {
+      for (int b = 0; b < L.nblk - 1; ++b) {
         const float2_t v = sp[b];
         s1 += v.x;
         s2 += v.y;
       }
+      float2_t last = sp[L.nblk - 1];
+      if (rl == tail_rl) last = *(const float2_t*)(base + nvalid - 2);
+      s1 += last.x;
+      s2 += last.y;
       const float delta = s1 * inv_k;
       const float var = fmaxf(s2 * inv_k - delta * delta, 0.0f);
       rowinfo[rl] = float2_t{delta, rsqrtf(var + L.eps)};

@@ -220,3 +220,204 @@ def repack_ref(qweight: np.ndarray, layout: int) -> np.ndarray:
         out |= q[k0 + j, col] << np.uint32(4 * pos)
     return out.view(np.int32)
 
+
+
+# ------------------------------------------------------------------ LayerNorm fold and gated MLP
+# (test_w4a16_lnf_gated.py)
+U24 = 2.0 ** -24             # half an fp32 ulp, relative: the error of one fp32 rounding
+LNF_EPS = float(np.float32(1e-6))
+LNF_MS = (1, 31, 33, 255, 256, 257, 2 * 256 + 13)
+RSQRT_U = 2                  # rsqrtf: 1 ulp in the HIP math API's accuracy table = 2 * 2^-24 relative
+
+
+def check_interval_f16(got: np.ndarray, y: np.ndarray, e: np.ndarray):
+    """fp16 outputs against a float64 reference y with a per-element bound e: an output passes iff
+    float16(y - e) <= got <= float16(y + e) (check_gelu_f16 with any bound; a NaN never passes).
+    Returns (violations, the largest need / e over the finite outputs that differ from float16(y),
+    need = the distance of y from the fp16 rounding boundary on got's side: the bound that output
+    would have needed)."""
+    e = np.broadcast_to(np.asarray(e, np.float64), y.shape)
+    lo, hi = (y - e).astype(np.float16), (y + e).astype(np.float16)
+    bad = ~((got >= lo) & (got <= hi))
+    ref = y.astype(np.float16)
+    diff = (got != ref) & np.isfinite(got)
+    if not diff.any():
+        return int(bad.sum()), 0.0
+    go = got[diff]
+    edge = (go.astype(np.float64) + np.nextafter(go, ref[diff]).astype(np.float64)) / 2
+    return int(bad.sum()), float((np.abs(edge - y[diff]) / e[diff]).max())
+
+
+class LnfProducer:
+    """RESADD_LNF operands and float64 expectations on the first n columns of a problem:
+    x_new = y_resadd (exact in fp32), mu_p a multiple of 2^-12 within about 0.5 of the row mean and
+    different in every row, gamma from {1, 2, 4}.  x_new is a multiple of 2^-14 below 512 and so is
+    d = x_new - mu_p (below 1024: 24 bits), hence d and d * gamma are exact in fp32 and aout is ONE
+    rounding of the float64 d * gamma; d != 0 is at least 2^-14, no fp16 subnormal."""
+
+    def __init__(self, p: Problem, n: int):
+        rng = np.random.Generator(np.random.PCG64([p.k, p.group, n, 7]))
+        x = p.y_resadd[:, :n]
+        off = (rng.permutation(p.m) + 0.5) / p.m - 0.5               # distinct, inside (-0.5, 0.5)
+        t, seen = np.round((x.mean(1) + off) * 4096).astype(np.int64), set()
+        for r in range(p.m):                                         # a value taken by an earlier row: one step up
+            while int(t[r]) in seen:
+                t[r] += 1
+            seen.add(int(t[r]))
+        mu = t / 4096.0
+        self.n, self.x = n, x
+        self.mu = mu.astype(np.float32)
+        self.gamma = (2.0 ** rng.integers(0, 3, n)).astype(np.float32)
+        self.d = x - mu[:, None]
+        self.aout64 = self.d * self.gamma.astype(np.float64)[None, :]
+        self.aout = self.aout64.astype(np.float16)
+        blk = self.d.reshape(p.m, n // 64, 64)
+        self.s1, self.s2, self.sa = blk.sum(2), (blk * blk).sum(2), np.abs(blk).sum(2)
+
+    def stats_bounds(self):
+        """lnf_res4 + sum16_dpp: a lane adds its 4 columns as (d0 + d1) + (d2 + d3) (two levels),
+        four DPP levels follow: 6 roundings on any path to the total, |s1 - S1| <= 6 u sum|d|;
+        the squares add one rounding each and the terms are positive: |s2 - S2| <= 8 u S2 (the 7
+        first-order roundings rounded up)."""
+        return 6 * U24 * self.sa, 8 * U24 * self.s2
+
+    def stats_violations(self, got: np.ndarray, m: int) -> int:
+        """got (m, n / 64, 2): the number of block sums outside their bound."""
+        b1, b2 = self.stats_bounds()
+        g = got.astype(np.float64)
+        return int((~(np.abs(g[..., 0] - self.s1[:m]) <= b1[:m])).sum() +
+                   (~(np.abs(g[..., 1] - self.s2[:m]) <= b2[:m])).sum())
+
+
+@functools.lru_cache(maxsize=None)
+def lnf_producer(k: int, group: int, n: int) -> LnfProducer:
+    return LnfProducer(problem(k, group), n)
+
+
+def _zigzag(nblk: int) -> np.ndarray:
+    """nblk values evenly spaced over [0.5, 1.5], ordered low, high, low, ...: neighbours lie half
+    the range apart."""
+    v = np.linspace(0.5, 1.5, nblk) if nblk > 1 else np.ones(1)
+    lo, hi = v[:(nblk + 1) // 2], v[(nblk + 1) // 2:]
+    out = np.empty(nblk)
+    out[0::2], out[1::2] = lo, hi
+    return out
+
+
+class LnfStats:
+    """Synthetic consumer ``stats`` (rows x K / 64 x 2, fp32), independent of any producer: row r has
+    its own variance, about 0.25 * 64^u in [0.25, 16] (even rows u in [0, 0.4], odd rows [0.6, 1]:
+    neighbouring rows lie a factor 2.3 or more apart) and its own delta, 0.3 .. 1 times sqrt(var) / 2
+    of either sign.  The row totals S1 = K delta and S2 = K (var + delta^2) are dealt over the
+    blocks by two different zigzag weight vectors (neighbouring blocks differ by half the mean
+    block and more; every s1 of a row has one sign, every s2 is positive, so the sums lose no
+    bits to cancellation).  delta, var and rstd are recomputed in float64 from the fp32 pairs."""
+
+    def __init__(self, k: int, m: int = MAXM):
+        self.k, self.nblk = k, k // 64
+        nb = self.nblk
+        rng = np.random.Generator(np.random.PCG64([k, m, 11]))
+        rows = np.arange(m)
+        u = 0.6 * (rows % 2) + 0.4 * (rng.permutation(m) + 0.5) / m
+        var = 0.25 * 64.0 ** u
+        delta = rng.choice([-1.0, 1.0], m) * np.sqrt(var) / 2 * rng.uniform(0.3, 1.0, m)
+        w1 = _zigzag(nb)[None, :] * rng.uniform(1.0, 1.05, (m, nb))
+        w2 = _zigzag(nb)[::-1][None, :] * rng.uniform(1.0, 1.05, (m, nb))
+        st = np.empty((m, nb, 2), np.float32)
+        st[..., 0] = (k * delta)[:, None] * w1 / w1.sum(1, keepdims=True)
+        st[..., 1] = (k * (var + delta * delta))[:, None] * w2 / w2.sum(1, keepdims=True)
+        self.stats = st
+        self.delta, self.var, self.rstd = self.rowinfo(st)
+        self.mu0 = (rng.choice([-1.0, 1.0], m) * rng.uniform(8.0, 16.0, m)).astype(np.float32)
+
+    def rowinfo(self, st):
+        s = st.astype(np.float64).sum(1)
+        delta = s[:, 0] / self.k
+        var = s[:, 1] / self.k - delta * delta
+        with np.errstate(invalid="ignore"):
+            return delta, var, 1.0 / np.sqrt(var + LNF_EPS)
+
+
+@functools.lru_cache(maxsize=None)
+def lnf_stats(k: int) -> LnfStats:
+    return LnfStats(k)
+
+
+def lnf_consts(k: int, n: int):
+    """The consumer's gw, bw: small fp32 vectors, |gw| <= 2, |bw| <= 1."""
+    rng = np.random.Generator(np.random.PCG64([k, n, 13]))
+    return rng.uniform(-2, 2, n).astype(np.float32), rng.uniform(-1, 1, n).astype(np.float32)
+
+
+def lnf_c(nblk: int) -> int:
+    """The count of fp32 roundings between the staged pairs and the fp32 value the consumer converts
+    to fp16 (lnf_rowinfo_wg, lnf_out8 in csrc/gemm_w4a16.hip), each at most 2^-24 relative:
+
+    * nblk - 1   the adds of a row's nblk pairs (the first add, to 0, is exact);
+    * 3          inv_k = 1 / K and its two products s1 * inv_k, s2 * inv_k;
+    * 1          the variance subtraction s2 * inv_k - delta^2 (|delta|^2 <= var / 4 on the test's
+                 inputs, so it amplifies what it subtracts by at most 1.5);
+    * RSQRT_U    rsqrtf: 1 ulp = 2 * 2^-24 in the HIP math API's accuracy table;
+    * 2          the two fmas of lnf_out8, fma(rstd, fma(-delta, gw, v), bw + bias).
+
+    c = nblk + 5 + RSQRT_U, applied to the magnitude of the terms that carry the roundings,
+    E = c 2^-24 (|rstd| (|acc s| + |delta gw|) + |bw + bias|).  The count treats the roundings as
+    one chain; the fp32 sum bw + bias, the + eps and the second use of delta^2 are covered by the
+    terms that the chain counts against the whole magnitude although they touch only part of it
+    (the delta path's nblk + 1 roundings reach |delta gw| alone, the rstd path halves what the
+    variance collected)."""
+    return nblk + 5 + RSQRT_U
+
+
+def lnf_consumer_ref(p: Problem, rowinfo, m: int, n: int, gw, bw, bias, act: bool, mat=None, c=None):
+    """float64 y = rstd (acc s - delta gw) + bw + bias (-> GELU) for rows [:m], columns [:n] and its
+    bound E (GELU: 1.13 E + GELU_E, 1.13 bounding |GELU'|).  mat: acc s if not the problem's."""
+    delta, _, rstd = (x[:m, None] for x in rowinfo)
+    mat = p.acc[:m, :n] * p.qn[None, :n] if mat is None else mat
+    gw, bb = gw.astype(np.float64)[None, :], bw.astype(np.float64)[None, :]
+    if bias is not None:
+        bb = bb + bias.astype(np.float64)[None, :n]
+    y = rstd * (mat - delta * gw) + bb
+    c = lnf_c(p.k // 64) if c is None else c
+    e = c * U24 * (np.abs(rstd) * (np.abs(mat) + np.abs(delta * gw)) + np.abs(bb))
+    if act:
+        with np.errstate(invalid="ignore"):
+            return gelu(y), 1.13 * e + GELU_E
+    return y, e
+
+
+# ---- gated MLP: gate = columns [0, n), up = columns [n, 2n) of a problem, bias dropped
+GATED_ROWS = (5, 8)          # the all +amax and all -amax rows
+
+
+def gated_scale(k: int) -> int:
+    """A rows GATED_ROWS times 4 at K = 64 (gates past +-20 there too); exact in fp16 and fp32."""
+    return 4 if k == 64 else 1
+
+
+def gated_a(p: Problem) -> np.ndarray:
+    a = p.a.copy()
+    a[list(GATED_ROWS)] *= np.float16(gated_scale(p.k))
+    return a
+
+
+def gated_ref(p: Problem, n: int):
+    """float64 gate g, up u and silu(g) * u = g / (1 + exp(-g)) * u of the scaled A."""
+    acc = p.acc[:, :2 * n].copy()
+    acc[list(GATED_ROWS)] *= gated_scale(p.k)
+    g, u = acc[:, :n] * p.qn[None, :n], acc[:, n:2 * n] * p.qn[None, n:2 * n]
+    with np.errstate(over="ignore"):
+        return g, u, g / (1.0 + np.exp(-g)) * u, acc
+
+
+def interleave32_ref(gate_words, up_words, gate_sc, up_sc, gate_qz, up_qz, k: int):
+    """samq_w4a16_gated_mlp's operand layout from the comment of ops.w4_interleave32, as a gather
+    over the output index: 32-column block B of the 2N columns is block B // 2 of the gate (B even)
+    or of the up projection (B odd).  A block is (K / 64) * 256 consecutive words of a layout-1
+    matrix, 32 scales of a group row and 4 qzeros words (8 columns each) of a group row."""
+    def gather(gate, up, per_block):
+        i = np.arange(2 * gate.shape[-1])
+        b, inner = i // per_block, i % per_block
+        src = (b // 2) * per_block + inner
+        return np.where(b % 2 == 0, gate[..., src], up[..., src])
+    return (gather(gate_words, up_words, k // 64 * 256), gather(gate_sc, up_sc, 32), gather(gate_qz, up_qz, 4))
