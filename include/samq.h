@@ -64,8 +64,8 @@ int samq_w4_repack(const int32_t* qweight, int32_t* packed, int K, int N, hipStr
 
 /* Same with an explicit fragment layout: 1 = the W4A16 layout (32x32x16 MFMA order, what
  * samq_w4_repack produces and every samq_w4a16_gemm_cfg config of this library consumes),
- * 3 = the W4A8 layout (samq_w4a8_gemm / samq_i8_gemm_cfg).  Layout 2 exists only in the
- * tuning build (make tuning); this library rejects it with SAMQ_ERR_INVALID. */
+ * 3 = the W4A8 layout (samq_w4a8_gemm / samq_i8_gemm_cfg).  Any other value returns
+ * SAMQ_ERR_INVALID. */
 int samq_w4_repack_layout(const int32_t* qweight, int32_t* packed, int K, int N, int layout,
                           hipStream_t stream);
 
@@ -80,14 +80,32 @@ int samq_w4a16_gemm(const void* A, int64_t lda, const int32_t* wpacked, const vo
                     int K, int groupsize, int epilogue, hipStream_t stream);
 
 /* Same with an explicit tile configuration (0 = automatic); for tests and in-graph A/B runs.
- * All accept layout-1 weights and compute the same result (up to fp32 summation order):
- *   1 256x256  2 256x128  3 128x128  4 64x64  5 64x32  6 128x256 (1 wave row)  7 256x256
- *   (8 waves in N)  9 128x256                               -- v1, register-staged
- *   21 256x256  22 128x256  23 128x128  24 256x128  25 128x256  26 64x64
- *   29 128x320  30 256x320  31 128x320                      -- v3, LDS-DMA ring
- *   55 56 57 58 62 64 65 (groupsize == K only)             -- v6 ping-pong, 256x256
- * Any other value (the tuning build's timing-only and layout-2 configs) returns
- * SAMQ_ERR_INVALID. */
+ * All accept layout-1 weights and compute the same result (up to fp32 summation order).  N must
+ * be a multiple of the tile's BN (BM x BN below).
+ *   v1, register-staged B; any C alignment; per-channel and grouped weights:
+ *     1 256x256  2 256x128  3 128x128  4 64x64  5 64x32  6 128x256 (1 wave row)
+ *     7 256x256 (8 waves in N)  9 128x256
+ *   v3, LDS-DMA ring; C 16-byte aligned, ldc % 8 == 0; per-channel and grouped weights:
+ *     21 256x256  22 128x256  23 128x128  24 256x128  25 128x256 (1 wave row)  26 64x64
+ *     29 128x320  30 256x320  31 128x320 (1 wave row)
+ *   v6 ping-pong, all 256x256; C 16-byte aligned, ldc % 8 == 0:
+ *     55  3 ring slots, lookahead 2          56  4 slots, lookahead 2
+ *     57  4 slots, lookahead 3 (the default for wide N)
+ *     58  56 with one phase per K tile       62  4x2 waves of 64x128 instead of 2x4 of 128x64
+ *     64  57 on 16x16x32 MFMA (the default for N < 2048)      65  56 on 16x16x32 MFMA
+ *     100 / 101  57 / 64 with the LDS-DMA issue spread through the MFMA burst
+ *     104  57 with transposed accumulators and an f16-staged epilogue: SAMQ_EPI_BIAS /
+ *          SAMQ_EPI_BIAS_GELU only (SAMQ_ERR_UNSUPPORTED for the f32 outputs)
+ *     107 / 108  57 / 64 persistent (one workgroup per CU loops over the tiles)
+ *     109 / 110  57 / 64 with the epilogue's scale / bias loaded before the main loop
+ *     111  57 with f16 outputs staged transposed (f32 outputs run 57 itself)
+ *     112 / 113  for grouped weights 57 / 64 with the group rows prefetched into registers;
+ *          for per-channel weights 57 / 64 themselves
+ *     114  57 (the grouped form of 57 under its own id)
+ *   Of the ping-pong configs 57, 64, 112, 113 and 114 take grouped weights (groupsize < K); the
+ *   others return SAMQ_ERR_INVALID for them.
+ * Any other id (the tuning build's timing-only configs among them) returns SAMQ_ERR_INVALID
+ * with "unknown tile config". */
 int samq_w4a16_gemm_cfg(const void* A, int64_t lda, const int32_t* wpacked, const void* scales,
                         const int32_t* qzeros, const void* bias, void* C, int64_t ldc, int M,
                         int N, int K, int groupsize, int epilogue, int cfg, hipStream_t stream);

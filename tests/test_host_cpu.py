@@ -58,23 +58,37 @@ def test_c_abi_empty_batch_is_a_no_op():
 
 
 def test_c_abi_rejects_timing_and_layout2_configs():
-    """The product library exposes only tile configs that compute the GEMM on layout-1 weights:
-    the tuning build's timing-only variants (27/28 no unpack, 70-73 no MFMA / no restaging) and the
-    layout-2 v4 kernels (41-45) are rejected before any device work (no launch happens)."""
+    """The product library's tile-config table holds exactly ops.W4A16_CFGS: every other id -- the
+    tuning build's timing-only variants (70-72, 102, 103) and the ids of retired experiments among
+    them -- answers "unknown tile config"; a known id answers "N not divisible by tile" for an N
+    that is no multiple of its BN, and every v3 / ping-pong id refuses a C that is not 16-byte
+    aligned.  Packed layout 2 no longer exists.  All of it before any device work (no launch
+    happens: the pointers are not device memory)."""
     from samq import _lib, ops
     from samq.quant_linear import QuantLinear
+    import test_w4a16_gemm as G
     lib = _lib.load()
     p = ctypes.c_void_p(4096)
-    for cfg in range(1, 120):
+
+    def gemm(cfg, n, c=p):
+        st = lib.samq_w4a16_gemm_cfg(p, 1280, p, p, p, None, c, 4096, 256, n, 1280, -1, 0, cfg, None)
+        return st, lib.samq_last_error().decode()
+
+    for cfg in range(1, 256):
         if cfg in ops.W4A16_CFGS:
             continue
-        st = lib.samq_w4a16_gemm_cfg(p, 1280, p, p, p, None, p, 1280, 256, 1280, 1280, -1, 0, cfg, None)
-        assert st == _lib.SAMQ_ERR_INVALID, cfg
-    assert "unknown tile config" in lib.samq_last_error().decode() or "N not divisible" in lib.samq_last_error().decode()
-    for cfg in (27, 41, 71):
-        st = lib.samq_w4a16_gemm_cfg(p, 1280, p, p, p, None, p, 1280, 256, 1280, 1280, -1, 0, cfg, None)
-        assert st == _lib.SAMQ_ERR_INVALID
+        st, msg = gemm(cfg, 1280)
+        assert st == _lib.SAMQ_ERR_INVALID and "unknown tile config" in msg, (cfg, st, msg)
+    assert set(G.TILES) == set(ops.W4A16_CFGS)
+    for cfg, (_, bn) in G.TILES.items():
+        if bn > 32:
+            st, msg = gemm(cfg, bn + 32)
+            assert st == _lib.SAMQ_ERR_INVALID and "N not divisible by tile" in msg, (cfg, st, msg)
+    for cfg in G.V3_CFGS + G.PP_CFGS:
+        st, msg = gemm(cfg, 3 * G.TILES[cfg][1], ctypes.c_void_p(4096 + 2))
+        assert st == _lib.SAMQ_ERR_INVALID and "16-byte aligned C" in msg, (cfg, st, msg)
     assert lib.samq_w4_repack_layout(p, p, 1280, 1280, 2, None) == _lib.SAMQ_ERR_INVALID
+    assert "layout must be 1 or 3" in lib.samq_last_error().decode()
     q = QuantLinear(4, -1, 256, 256, True)
     for cfg in (71, 41, 27):
         with pytest.raises(ValueError):
