@@ -370,7 +370,7 @@ int samq_attention_relbias(const void* inp, const void* rel_h, const void* rel_w
  *   out  int8 [B, H, W, heads*hd] = q8(softmax(scores) . (v*s_qkv), s_out)     (qact2)
  * window > 0: S x S windows over the grid padded to a multiple of S (pad tokens' q/k/v =
  * q8(qkv_bias f32 [3*heads*hd], s_qkv), or 0 if qkv_bias is NULL), window <= 16;
- * window == 0: global over an H == W <= 64 grid.  hd must be 64 (else SAMQ_ERR_UNSUPPORTED). */
+ * window == 0: global over an H == W <= 64 grid.  hd 64 or 80 (else SAMQ_ERR_UNSUPPORTED). */
 int samq_rel_attention_q8(const int8_t* qkv, const float* qkv_bias, const float* rel_pos_h,
                           const float* rel_pos_w, int8_t* out, int B, int H, int W, int heads,
                           int hd, int window, float sm_scale, float s_qkv, float s_a1, float s_a2,

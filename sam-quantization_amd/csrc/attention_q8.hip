@@ -27,10 +27,10 @@
 namespace samq {
 
 struct AttnQ8Params {
-  const int8_t* qkv;        // [B, H, W, 3, heads, 64] codes
+  const int8_t* qkv;        // [B, H, W, 3, heads, D] codes (D = 64 or 80)
   const float* qkv_bias;    // [3 * C] f32 or null (pad tokens)
-  const float* relh;        // [2S-1, 64] f32
-  const float* relw;        // [2S-1, 64] f32
+  const float* relh;        // [2S-1, D] f32
+  const float* relw;        // [2S-1, D] f32
   int8_t* out;              // [B, H, W, C] codes
   int B, H, W, heads, C, S, window, nwh, nww, L;
   const _Float16* v16;      // optional [B, H, W, C] fp16 copy of the V codes (samq_w8a8_gemm_v16)
@@ -46,15 +46,42 @@ __device__ __forceinline__ float aq8(float v, float s) {
   return q8_exact(v, s, 1.0f / s);   // s is a kernel argument: the reciprocal is hoisted
 }
 
-constexpr int QD = 64;       // head dim (vit_b)
+// Head dim D is a template parameter of every kernel here: 64 (vit_b, vit_l) or 80 (vit_h).  D = 80
+// is 5 sixteen-byte pieces per token and head; dims 64..79 enter q.k through a second
+// v_mfma_i32_16x16x64_i8 into the same int32 tile, with lane group 0 holding the 16 dims and groups
+// 1..3 zero in BOTH operands (q8_tail).  The cheaper v_mfma_i32_16x16x32_i8 (4 passes instead of 8)
+// must not be chained onto the 16x16x64 result: with SrcC = the previous vDst the compiler leaves the
+// two back to back, which the hardware supports for MFMAs of equal pass count only -- on gfx950 the
+// 4-pass instruction read the tile before the 8-pass one had written it (wrong scores wherever no
+// LDS wait happened to fall between them).  The MFMA pipe has the room: these loops are VALU-bound.
+// Dims 64..79 of the token whose head starts at ``base``, in lane group 0; zero in groups 1..3.
+__device__ __forceinline__ int4v q8_tail(const int8_t* base, int g) {
+  const int4v v = *(const int4v*)(base + 64);
+  const int4v z = {0, 0, 0, 0};
+  return g == 0 ? v : z;
+}
+// the same from the qkv bias (pad tokens): q8(bias) codes of dims 64..79
+__device__ __forceinline__ int4v q8_tail_bias(const float* bias, float s, int g) {
+  int4v w = {0, 0, 0, 0};
+#pragma unroll
+  for (int e = 0; e < 16; ++e) w[e >> 2] |= ((int)q8_exact(bias[64 + e], s, 1.0f / s) & 0xFF) << (8 * (e & 3));
+  const int4v z = {0, 0, 0, 0};
+  return g == 0 ? w : z;
+}
 
 __device__ __forceinline__ float q8max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-constexpr int KPITCH = 80;   // K row pitch in LDS (bytes) of the generic kernel (the row64 / window kernels use 96)
+// K row pitch in LDS (bytes) of the generic kernel: 80 at D = 64; a D = 80 row is 80 bytes itself, so
+// it takes the 96 of the row64 / window kernels (resident, 16 waves: 126 KiB of LDS, one workgroup
+// per CU as at D = 64 with its 107 KiB)
+template <int D> constexpr int q8_kpitch() { return D == 64 ? 80 : 96; }
 
 // ROW64: global attention over a 64-wide grid -- a 64-key chunk is exactly one key row, so the
 // height term is one value per chunk and the width term a fixed per-lane set (registers).
-template <bool RESIDENT, int NWQ, int KC, int MAXS, bool ROW64 = false>
+template <int D, bool RESIDENT, int NWQ, int KC, int MAXS, bool ROW64 = false>
 __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params p) {
+  static_assert(D == 64 || D == 80, "head dim");
+  constexpr int QD = D, KPITCH = q8_kpitch<D>();
+  constexpr int PARTS = D / 16;                  // 16-byte pieces per token and head
   constexpr int NBUF = RESIDENT ? 1 : 2;
   constexpr int VTP = KC + 8;                    // V^T row pitch (halves)
   __shared__ __attribute__((aligned(16))) int8_t k_lds[NBUF][KC * KPITCH];
@@ -68,6 +95,7 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
   const int wave = tid >> 6;
   const int g = lane >> 4;
   const int ql = lane & 15;
+  const int qlt = g == 0 ? ql : 0;   // D = 80: K row of the tail fragment (groups 1..3 re-read row 0: a broadcast, no bank conflict)
   const int S = p.S, L = p.L, C = p.C;
   const int head = blockIdx.y;
   int b, wy = 0, wx = 0;
@@ -94,7 +122,7 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
 
   // ---- stage keys [c0, c0 + KC) of K (codes) and V^T (fp16) into buffer buf
   auto stage = [&](int c0, int buf) {
-    for (int u = tid; u < KC * 4; u += 64 * NWQ) {
+    for (int u = tid; u < KC * PARTS; u += 64 * NWQ) {
       const int key = u % KC, part = u / KC;
       const int kk = c0 + key;
       u32x4 kc = {0u, 0u, 0u, 0u}, vc = {0u, 0u, 0u, 0u};
@@ -129,6 +157,7 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
   int qy = 0, qx = 0;
   bool q_ok = false;
   int4v qfrag = {0, 0, 0, 0};
+  int4v qtail = {0, 0, 0, 0};                    // D = 80: dims 64..79 (q8_tail)
   if (qt < L) {
     tok(qt, qy, qx);
     bool inimg;
@@ -136,15 +165,19 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
     q_ok = inimg;
     if (inimg) {
       qfrag = *(const int4v*)(tp + head * QD + g * 16);
+      if constexpr (D == 80) qtail = q8_tail(tp + head * QD, g);
     } else if (p.qkv_bias) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int qq = (int)aq8(p.qkv_bias[head * QD + g * 16 + e], p.s_qkv);
         qfrag[e >> 2] |= (qq & 0xFF) << (8 * (e & 3));
       }
+      if constexpr (D == 80) qtail = q8_tail_bias(p.qkv_bias + head * QD, p.s_qkv, g);
     }
   }
   *(int4v*)(&q_lds[wave][ql * KPITCH + g * 16]) = qfrag;
+  if constexpr (D == 80)
+    if (g == 0) *(int4v*)(&q_lds[wave][ql * KPITCH + 64]) = qtail;
   __builtin_amdgcn_s_waitcnt(0xC07F);
   {
     // rel_h[q][kh] = sum_d (code_q[d] * s_qkv) * Rh[qy - kh + S - 1][d];  rel_w likewise with Rw and
@@ -219,7 +252,10 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
     for (int bb = 0; bb < 4; ++bb) {
       const int4v kf = *(const int4v*)(&k_lds[buf][(koff + bb * 16 + ql) * KPITCH + g * 16]);
       const int4v z = {0, 0, 0, 0};
-      const int4v st = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qfrag, z, 0, 0, 0);
+      int4v st = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qfrag, z, 0, 0, 0);
+      if constexpr (D == 80)
+        st = __builtin_amdgcn_mfma_i32_16x16x64_i8(q8_tail(&k_lds[buf][(koff + bb * 16 + qlt) * KPITCH], g), qtail, st,
+                                                   0, 0, 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float c;
@@ -311,8 +347,14 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
 // exact in fp16); the f32 tables enter as fp16 hi + lo pairs (|R - hi - lo| <= 2^-22 |R|), so the
 // sums carry fp32-level error like a scalar fp32 dot product (whose order differs from the
 // reference's anyway).  Lane (ql, g) receives rel[16 bb + 4 g + i][query ql], i = 0..3.
+// D = 80 = 2 x 32 + 16: dims 64..79 go through a third, half-filled 16x16x32 step (lane groups 0 / 1
+// hold dims 64 + 8g .. + 7, groups 2 / 3 are zero in BOTH operands -- a table value times a zero code
+// would still be NaN for an Inf) rather than a 16x16x16: one opcode along the accumulate chain (see
+// q8_tail).
+template <int D>
 __device__ __forceinline__ void q8_rel_block(const AttnQ8Params& p, const int8_t* qcodes_lane, int qy, int side,
                                              int bb, int lane, float4_t& rh4, float4_t& rw4) {
+  constexpr int QD = D;
   const int ql = lane & 15, g = lane >> 4;
   int r = qy - (16 * bb + ql) + side - 1;      // table row of this lane's A row (kk = 16 bb + ql)
   r = r < 0 ? 0 : (r > 2 * side - 2 ? 2 * side - 2 : r);   // rows past the window: any valid row (masked)
@@ -332,6 +374,31 @@ __device__ __forceinline__ void q8_rel_block(const AttnQ8Params& p, const int8_t
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float x = e < 4 ? x0[e] : x1[e - 4];
+        hi[e] = (_Float16)x;
+        lo[e] = (_Float16)(x - (float)hi[e]);
+      }
+      float4_t& d = tab ? rw4 : rh4;
+      d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi, qb, d, 0, 0, 0);
+      d = __builtin_amdgcn_mfma_f32_16x16x32_f16(lo, qb, d, 0, 0, 0);
+    }
+  }
+  if constexpr (D % 32 == 16) {
+    constexpr int T0 = D - 16;
+    const bool on = g < 2;
+    const int toff = T0 + 8 * (g & 1);          // groups 2 / 3 read what 0 / 1 read, and zero it
+    const uint2 cw = *(const uint2*)(qcodes_lane + toff);
+    half8_t qb;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      qb[e] = on ? (_Float16)(float)(int8_t)((((e < 4) ? cw.x : cw.y) >> (8 * (e & 3))) & 0xFFu) : (_Float16)0.f;
+#pragma unroll
+    for (int tab = 0; tab < 2; ++tab) {
+      const float* src = (tab ? p.relw : p.relh) + (int64_t)r * QD + toff;
+      const float4_t x0 = *(const float4_t*)src, x1 = *(const float4_t*)(src + 4);
+      half8_t hi, lo;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float x = on ? (e < 4 ? x0[e] : x1[e - 4]) : 0.f;
         hi[e] = (_Float16)x;
         lo[e] = (_Float16)(x - (float)hi[e]);
       }
@@ -416,15 +483,31 @@ __device__ __forceinline__ void q8_ptab_unpack(const uint32_t (&w)[8], half8_t& 
 // key row's store, after the prologue barrier), so three workgroups still fit a CU.  Kernel 120.3 ->
 // 118.5 us per vit_b launch, bit-identical (profiles/r6_w8a8_row64_variants.log; that log also holds
 // the measured-slower speculative P-table reads and the LDS-free direct-from-L2 prototype).
-template <int NWQ, bool V16 = false>
+// D = 80 (vit_h) keeps both pitches.  K: 96 bytes hold the 80.  V: 80 halves is now the row itself, no
+// pad, and still the conflict-free choice for the tr reads -- a 32-lane group reads 8 key rows x 32
+// bytes, row r starting at bank 40 r mod 64 = 8 (5r mod 8), a permutation of the eight 8-bank slots,
+// for every tile t (a tile shifts all rows alike); 88 halves (44 banks a row) puts rows 0 / 3 and 96
+// (48 banks) rows 0 / 4 on the same banks.  LDS is then the D = 64 figure, 51456 bytes, three
+// workgroups per CU.  The tail K fragment (ds_read_b128 at byte 64 of row ql, lane group 0 only; rows
+// ql and ql + 8 are 768 bytes = 3 bank rows apart, but never meet in one 16-lane group of the read once
+// groups 1..3 all re-read row 0) is conflict-free too.  Staging: the 5th piece
+// of each key (dims 64..79) is 64 K pieces + 64 (int8 V) or 128 (fp16 V) V pieces per chunk on top of
+// the 256 threads' one piece of dims 0..63 each, so every thread issues one more 16-byte load per
+// chunk, its source picked by the wave -- wave 0: K tail of key = lane; int8 V: wave 1 the V tail;
+// fp16 V: waves 1 / 2 its two halves; the remaining waves repeat wave 0's load (a cache hit) and store
+// nothing -- the loads stay unconditional, so the waits stay counted.
+template <int D, int NWQ, bool V16 = false>
 __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(AttnQ8Params p) {
+  static_assert(D == 64 || D == 80, "head dim");
+  constexpr int QD = D;
   constexpr int G = 64, KC = 64;
   constexpr int KP = 96;                         // K row pitch (bytes)
-  constexpr int VP = QD + 16;                    // V row pitch (halves)
+  constexpr int VP = 80;                         // V row pitch (halves)
   constexpr int NT = 64 * NWQ;
-  constexpr int UNITS = KC * 4;                  // 16-byte pieces of one chunk's K (and of its V)
+  constexpr int UNITS = KC * 4;                  // 16-byte pieces of dims 0..63 of one chunk's K (and of its V)
   static_assert(UNITS % NT == 0, "staging");
   constexpr int UPT = UNITS / NT;
+  static_assert(D == 64 || (NWQ == 4 && KC == 64), "tail staging: one key per lane, roles by wave");
   __shared__ __attribute__((aligned(16))) int8_t k_lds[2][KC * KP];
   __shared__ __attribute__((aligned(16))) _Float16 v_lds[2][KC * VP];
   int8_t(*q_lds)[16 * KP] = (int8_t(*)[16 * KP])(void*)&v_lds[1][0];   // prologue only
@@ -437,6 +520,7 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
   const int wave = tid >> 6;
   const int g = lane >> 4;
   const int ql = lane & 15;
+  const int qlt = g == 0 ? ql : 0;   // D = 80: K row of the tail fragment (groups 1..3 re-read row 0: a broadcast, no bank conflict)
   const int C = p.C;
   const int head = blockIdx.y;
   const int b = blockIdx.x;
@@ -451,8 +535,23 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
   // sets: chunk ch + 2 is loaded while chunk ch is computed and chunk ch + 1 (loaded one chunk
   // earlier) is stored -- two chunks of math to cover each load's latency
   u32x4 kreg[2][UPT], vreg[2][V16 ? 2 * UPT : UPT];
+  u32x4 treg[2];                                 // D = 80: this thread's tail piece (role by wave: see above)
   const _Float16* v16img = V16 ? p.v16 + (int64_t)b * G * G * C : nullptr;
+  // tail source of key = lane in key row 0, bytes; key rows are G tokens apart
+  const int8_t* tsrc = nullptr;
+  int64_t tstep = 0;
+  const int trole = V16 ? (wave == 3 ? 0 : wave) : (wave & 1);   // 0: K; 1: V (fp16 V: first half); 2: fp16 V second half
+  if constexpr (D == 80) {
+    if (V16 && trole > 0) {
+      tsrc = (const int8_t*)(v16img + (int64_t)lane * C + head * QD + 64 + 8 * (trole - 1));
+      tstep = (int64_t)G * C * 2;
+    } else {
+      tsrc = img + (int64_t)lane * ts + (1 + trole) * C + head * QD + 64;
+      tstep = (int64_t)G * ts;
+    }
+  }
   auto load = [&](int kh, int r) {
+    if constexpr (D == 80) treg[r] = *(const u32x4*)(tsrc + kh * tstep);
 #pragma unroll
     for (int j = 0; j < UPT; ++j) {
       const int u = tid + j * NT, key = u >> 2, part = u & 3;
@@ -468,6 +567,23 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
     }
   };
   auto store = [&](int buf, int r) {
+    if constexpr (D == 80) {
+      if constexpr (V16) {
+        if (wave == 0) *(u32x4*)(&k_lds[buf][lane * KP + 64]) = treg[r];
+        else if (wave < 3) *(u32x4*)(&v_lds[buf][lane * VP + 64 + 8 * (wave - 1)]) = treg[r];
+      } else if (wave == 0) {
+        *(u32x4*)(&k_lds[buf][lane * KP + 64]) = treg[r];
+      } else if (wave == 1) {
+        half8_t h0, h1;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          h0[e] = (_Float16)(float)(int8_t)((treg[r][e >> 2] >> (8 * (e & 3))) & 0xFFu);
+          h1[e] = (_Float16)(float)(int8_t)((treg[r][2 + (e >> 2)] >> (8 * (e & 3))) & 0xFFu);
+        }
+        *(half8_t*)(&v_lds[buf][lane * VP + 64]) = h0;
+        *(half8_t*)(&v_lds[buf][lane * VP + 64 + 8]) = h1;
+      }
+    }
 #pragma unroll
     for (int j = 0; j < UPT; ++j) {
       const int u = tid + j * NT, key = u >> 2, part = u & 3;
@@ -497,12 +613,17 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
   // workgroups fit a CU (the 768 workgroups of a vit_b launch are then all resident at once).
   const int4v qfrag = *(const int4v*)(img + ((int64_t)qy * G + qx) * ts + head * QD + g * 16);
   *(int4v*)(&q_lds[wave][ql * KP + g * 16]) = qfrag;
+  int4v qtail = {0, 0, 0, 0};
+  if constexpr (D == 80) {
+    qtail = q8_tail(img + ((int64_t)qy * G + qx) * ts + head * QD, g);
+    if (g == 0) *(int4v*)(&q_lds[wave][ql * KP + 64]) = qtail;
+  }
   __builtin_amdgcn_s_waitcnt(0xC07F);
   float rwr[4][4];
 #pragma unroll
   for (int bb = 0; bb < 4; ++bb) {
     float4_t rh4, rw4;
-    q8_rel_block(p, &q_lds[wave][ql * KP], qy, G, bb, lane, rh4, rw4);
+    q8_rel_block<D>(p, &q_lds[wave][ql * KP], qy, G, bb, lane, rh4, rw4);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       rh_lds[wave][ql * (G + 1) + 16 * bb + 4 * g + i] = rh4[i];
@@ -551,7 +672,9 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
     for (int bb = 0; bb < 4; ++bb) {
       const int4v kf = *(const int4v*)(&k_lds[buf][(bb * 16 + ql) * KP + g * 16]);
       const int4v z = {0, 0, 0, 0};
-      const int4v st = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qfrag, z, 0, 0, 0);
+      int4v st = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qfrag, z, 0, 0, 0);
+      if constexpr (D == 80)
+        st = __builtin_amdgcn_mfma_i32_16x16x64_i8(q8_tail(&k_lds[buf][(bb * 16 + qlt) * KP], g), qtail, st, 0, 0, 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float q1 = __builtin_amdgcn_fmed3f(__builtin_rintf((float)st[i] * c1), -128.f, 127.f);
@@ -630,10 +753,14 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
 // each staging the whole window's K / V: 14 x 14 windows of vit_b at B = 1 are 300 (window, head)
 // items on 256 CUs, so 44 CUs ran two whole items one after the other; as 600 half-items of 7 waves
 // the load spreads as ~2.3 half-items per CU.
-template <int SW, int NWQ = SW>
+// D = 80 on the same pitches (V rows of 80 halves are the unpadded row: see the row64 kernel), so the
+// LDS is the D = 64 figure (<14, 7>: 74816 bytes) and two workgroups still fit a CU.
+template <int D, int SW, int NWQ = SW>
 // two workgroups per CU: LDS <= 80 KiB and (HIP's second bound = waves per SIMD) <= 512 / (waves / 2) VGPRs
 __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_win_kernel(AttnQ8Params p) {
-  constexpr int SLOTS = 16 * SW, KP = 96, VP = QD + 16;   // conflict-free pitches: see the row64 kernel
+  static_assert(D == 64 || D == 80, "head dim");
+  constexpr int QD = D, PARTS = D / 16;                   // 16-byte pieces per token and head
+  constexpr int SLOTS = 16 * SW, KP = 96, VP = 80;        // conflict-free pitches: see the row64 kernel
   static_assert(SW % NWQ == 0, "query rows split evenly");
   constexpr int NCH = (SW + 3) / 4;                        // chunks of up to 4 key rows (64 slots)
   static_assert(SW <= 16, "one window per workgroup");
@@ -647,6 +774,7 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
   const int wave = tid >> 6;
   const int g = lane >> 4;
   const int ql = lane & 15;
+  const int qlt = g == 0 ? ql : 0;   // D = 80: K row of the tail fragment (groups 1..3 re-read row 0: a broadcast, no bank conflict)
   const int C = p.C;
   const int head = blockIdx.y;
   const int per = p.nwh * p.nww;
@@ -660,8 +788,8 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
   };
 
   // ---- stage K codes and V (fp16, row-major) of every key slot; pad tokens = q8(qkv bias)
-  for (int u = tid; u < SLOTS * 4; u += 64 * NWQ) {
-    const int slot = u >> 2, part = u & 3;
+  for (int u = tid; u < SLOTS * PARTS; u += 64 * NWQ) {
+    const int slot = PARTS == 4 ? u >> 2 : u / PARTS, part = PARTS == 4 ? u & 3 : u % PARTS;
     const int kh = slot >> 4, kw = slot & 15;
     u32x4 kc = {0u, 0u, 0u, 0u}, vc = {0u, 0u, 0u, 0u};
     if (kh < SW && kw < SW) {
@@ -697,24 +825,29 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
   const int qy = blockIdx.z * NWQ + wave, qx = q_in ? ql : 0;
   bool q_ok = false;
   int4v qfrag = {0, 0, 0, 0};
+  int4v qtail = {0, 0, 0, 0};                    // D = 80: dims 64..79 (q8_tail)
   if (q_in) {
     const int8_t* tp = tok_ptr(qy, qx, q_ok);
     if (q_ok) {
       qfrag = *(const int4v*)(tp + head * QD + g * 16);
+      if constexpr (D == 80) qtail = q8_tail(tp + head * QD, g);
     } else if (p.qkv_bias) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int qq = (int)aq8(p.qkv_bias[head * QD + g * 16 + e], p.s_qkv);
         qfrag[e >> 2] |= (qq & 0xFF) << (8 * (e & 3));
       }
+      if constexpr (D == 80) qtail = q8_tail_bias(p.qkv_bias + head * QD, p.s_qkv, g);
     }
   }
   *(int4v*)(&q_lds[wave][ql * KP + g * 16]) = qfrag;
+  if constexpr (D == 80)
+    if (g == 0) *(int4v*)(&q_lds[wave][ql * KP + 64]) = qtail;
   __builtin_amdgcn_s_waitcnt(0xC07F);
   float rwr[4];
   {
     float4_t rh4, rw4;
-    q8_rel_block(p, &q_lds[wave][ql * KP], qy, SW, 0, lane, rh4, rw4);
+    q8_rel_block<D>(p, &q_lds[wave][ql * KP], qy, SW, 0, lane, rh4, rw4);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       rwr[i] = rw4[i];
@@ -763,7 +896,9 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
       const float rh_row = rhq[kh] * inv2;
       const int4v kf = *(const int4v*)(&k_lds[(kh * 16 + ql) * KP + g * 16]);
       const int4v z = {0, 0, 0, 0};
-      const int4v st = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qfrag, z, 0, 0, 0);
+      int4v st = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qfrag, z, 0, 0, 0);
+      if constexpr (D == 80)
+        st = __builtin_amdgcn_mfma_i32_16x16x64_i8(q8_tail(&k_lds[(kh * 16 + qlt) * KP], g), qtail, st, 0, 0, 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float q1 = __builtin_amdgcn_fmed3f(__builtin_rintf((float)st[i] * c1), -128.f, 127.f);
@@ -841,7 +976,7 @@ extern "C" int samq_rel_attention_q8_rows(const int8_t* qkv, const float* qkv_bi
                                           float s_out, int row0, int rows, const void* v16, hipStream_t stream) {
   if (B == 0) return SAMQ_OK;   // empty batch: no work, data pointers may be null
   SAMQ_REQUIRE(qkv && rel_pos_h && rel_pos_w && out, SAMQ_ERR_INVALID, "rel_attention_q8: null pointer");
-  SAMQ_REQUIRE(hd == QD, SAMQ_ERR_UNSUPPORTED, "rel_attention_q8: head_dim must be 64");
+  SAMQ_REQUIRE(hd == 64 || hd == 80, SAMQ_ERR_UNSUPPORTED, "rel_attention_q8: head_dim must be 64 or 80");
   SAMQ_REQUIRE(B > 0 && H > 0 && W > 0 && heads > 0, SAMQ_ERR_INVALID, "rel_attention_q8: bad shape");
   SAMQ_REQUIRE(s_qkv > 0.f && s_a1 > 0.f && s_a2 > 0.f && s_out > 0.f, SAMQ_ERR_INVALID,
                "rel_attention_q8: scales must be > 0");
@@ -870,12 +1005,17 @@ extern "C" int samq_rel_attention_q8_rows(const int8_t* qkv, const float* qkv_bi
     const dim3 grid(B * p.nwh * p.nww, heads, 1);
     if (window == 14) {   // SAM's 14 x 14 windows: key and query rows of 16 slots, half a window per workgroup
       const dim3 grid2(B * p.nwh * p.nww, heads, 2);
-      hipLaunchKernelGGL((rel_attention_q8_win_kernel<14, 7>), grid2, dim3(64 * 7), 0, stream, p);
+      if (hd == 64) hipLaunchKernelGGL((rel_attention_q8_win_kernel<64, 14, 7>), grid2, dim3(64 * 7), 0, stream, p);
+      else hipLaunchKernelGGL((rel_attention_q8_win_kernel<80, 14, 7>), grid2, dim3(64 * 7), 0, stream, p);
     }
-    else if (p.L <= 13 * 16)
-      hipLaunchKernelGGL((rel_attention_q8_kernel<true, 13, 256, 16>), grid, dim3(64 * 13), 0, stream, p);
-    else
-      hipLaunchKernelGGL((rel_attention_q8_kernel<true, 16, 256, 16>), grid, dim3(64 * 16), 0, stream, p);
+    else if (p.L <= 13 * 16) {
+      if (hd == 64) hipLaunchKernelGGL((rel_attention_q8_kernel<64, true, 13, 256, 16>), grid, dim3(64 * 13), 0, stream, p);
+      else hipLaunchKernelGGL((rel_attention_q8_kernel<80, true, 13, 256, 16>), grid, dim3(64 * 13), 0, stream, p);
+    }
+    else {
+      if (hd == 64) hipLaunchKernelGGL((rel_attention_q8_kernel<64, true, 16, 256, 16>), grid, dim3(64 * 16), 0, stream, p);
+      else hipLaunchKernelGGL((rel_attention_q8_kernel<80, true, 16, 256, 16>), grid, dim3(64 * 16), 0, stream, p);
+    }
   } else {
     SAMQ_REQUIRE(H == W && H <= 64, SAMQ_ERR_UNSUPPORTED, "rel_attention_q8: global attention needs H == W <= 64");
     p.S = H; p.window = 0; p.nwh = p.nww = 1; p.L = H * W;
@@ -884,11 +1024,19 @@ extern "C" int samq_rel_attention_q8_rows(const int8_t* qkv, const float* qkv_bi
     p.row0 = row0;
     if (H == 64)   // one grid row of queries per workgroup (16 * NWQ == 64)
     {
-      if (v16) hipLaunchKernelGGL((rel_attention_q8_row64_kernel<NWQ, true>), dim3(B, heads, rows), dim3(64 * NWQ), 0, stream, p);
-      else hipLaunchKernelGGL((rel_attention_q8_row64_kernel<NWQ>), dim3(B, heads, rows), dim3(64 * NWQ), 0, stream, p);
+      const dim3 grid64(B, heads, rows);
+      if (hd == 64) {
+        if (v16) hipLaunchKernelGGL((rel_attention_q8_row64_kernel<64, NWQ, true>), grid64, dim3(64 * NWQ), 0, stream, p);
+        else hipLaunchKernelGGL((rel_attention_q8_row64_kernel<64, NWQ>), grid64, dim3(64 * NWQ), 0, stream, p);
+      } else {
+        if (v16) hipLaunchKernelGGL((rel_attention_q8_row64_kernel<80, NWQ, true>), grid64, dim3(64 * NWQ), 0, stream, p);
+        else hipLaunchKernelGGL((rel_attention_q8_row64_kernel<80, NWQ>), grid64, dim3(64 * NWQ), 0, stream, p);
+      }
     }
+    else if (hd == 64)
+      hipLaunchKernelGGL((rel_attention_q8_kernel<64, false, NWQ, 64, 64, false>), grid, dim3(64 * NWQ), 0, stream, p);
     else
-      hipLaunchKernelGGL((rel_attention_q8_kernel<false, NWQ, 64, 64, false>), grid, dim3(64 * NWQ), 0, stream, p);
+      hipLaunchKernelGGL((rel_attention_q8_kernel<80, false, NWQ, 64, 64, false>), grid, dim3(64 * NWQ), 0, stream, p);
   }
   SAMQ_LAUNCH_CHECK("rel_attention_q8 launch");
   return SAMQ_OK;

@@ -863,10 +863,15 @@ class ImageEncoderViT(nn.Module):
 
 
 def build_fq_image_encoder(name: str = "vit_b", img_size: int = 1024, cfg: Optional[Config] = None,
-                           depth: Optional[int] = None, quant=False, calibrate=False) -> ImageEncoderViT:
-    """fq_vit ``build_sam_vit_*`` encoder part (``fq_vit/models/sam/build_sam.py``)."""
+                           depth: Optional[int] = None, quant=False, calibrate=False,
+                           global_attn_indexes: Optional[Tuple[int, ...]] = None) -> ImageEncoderViT:
+    """fq_vit ``build_sam_vit_*`` encoder part (``fq_vit/models/sam/build_sam.py``).
+    ``global_attn_indexes``: the blocks with global attention; None keeps the named model's (a
+    shallow ``depth`` then has a global block only where one of them falls below it)."""
     from .build_sam import VIT_HPARAMS
     hp = VIT_HPARAMS[name]
+    if global_attn_indexes is not None:
+        hp = dict(hp, encoder_global_attn_indexes=tuple(global_attn_indexes))
     from functools import partial
     return ImageEncoderViT(depth=depth or hp["encoder_depth"], embed_dim=hp["encoder_embed_dim"], img_size=img_size,
                            mlp_ratio=4, norm_layer=partial(QIntLayerNorm, eps=1e-6),

@@ -1,8 +1,9 @@
 """Micro-benchmark of the W8A8 (fq_vit) attention kernels on the vit_b geometry (64 x 64 grid,
-12 heads of 64, windows of 14 and global), HIP events on the launch stream; outputs of every
-run compared with the first (determinism).  ``SAMQ_LIB`` selects a variant library.
+12 heads of 64, windows of 14 and global) or, ``--model vit_h``, the vit_h one (16 heads of 80), HIP
+events on the launch stream; outputs of every run compared with the first (determinism).
+``SAMQ_LIB`` selects a variant library.
 
-    python tools/bench_attn_q8.py [--batch 1] [--iters 20]
+    python tools/bench_attn_q8.py [--model vit_b] [--batch 1] [--iters 20]
 """
 import argparse
 import sys
@@ -17,6 +18,7 @@ from samq import ops  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("vit_b", "vit_h"), default="vit_b")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--window-only", action="store_true")
@@ -24,7 +26,8 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
-    b, side, heads, d = args.batch, 64, 12, 64
+    heads, d = {"vit_b": (12, 64), "vit_h": (16, 80)}[args.model]
+    b, side = args.batch, 64
     c = heads * d
     qkv = torch.randint(-100, 100, (b, side, side, 3 * c), generator=g, device=dev, dtype=torch.int8)
     bias = torch.randn(3 * c, generator=g, device=dev) * 0.1
@@ -51,7 +54,7 @@ def main():
                 e1.record(stream)
                 torch.cuda.synchronize()
                 b16 = min(b16, e0.elapsed_time(e1) / args.iters * 1e3)
-            print(f"attention_q8 window= 0 B={b} with fp16 V: {b16:8.1f} us", flush=True)
+            print(f"attention_q8 {args.model} window= 0 B={b} with fp16 V: {b16:8.1f} us", flush=True)
         best = 1e9
         for _ in range(3):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -65,7 +68,7 @@ def main():
         keys = (window * window) if window else side * side
         nq = b * side * side
         gop = 2 * 2 * nq * keys * d * heads / 1e9
-        print(f"attention_q8 window={window:2d} B={b}: {best:8.1f} us  {gop / best * 1e3:7.1f} TOPS (q.k + p.v)  "
+        print(f"attention_q8 {args.model} window={window:2d} B={b}: {best:8.1f} us  {gop / best * 1e3:7.1f} TOPS (q.k + p.v)  "
               f"deterministic: {same}", flush=True)
 
 
