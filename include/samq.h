@@ -386,6 +386,34 @@ int samq_rel_attention_q8_rows(const int8_t* qkv, const float* qkv_bias, const f
                                int window, float sm_scale, float s_qkv, float s_a1, float s_a2, float s_out,
                                int row0, int rows, const void* v16, hipStream_t stream);
 
+/* W8A8 attention of the mask decoder's two-way transformer (fq_vit quant-mode Attention.forward
+ * between the input projections and out_proj, fq_vit/models/sam/transformer.py:520-537) on int8
+ * codes; q [B, Nq, heads*hd] (qact1_1, s_q), k / v [B, Nk, heads*hd] (qact1_2 / qact1_3, s_k / s_v):
+ *   a   = q8(float(sum_d q k) * (s_q s_k / sqrt(hd)), s_a1)                 (qact_attn1; exact int32 sum)
+ *   out int8 [B, Nq, heads*hd] = q8(softmax(a * s_a1) . (v * s_v), s_out)   (qact2; fp32 softmax)
+ * hd 16 or 32 and heads*hd <= 256 (else SAMQ_ERR_UNSUPPORTED); any Nq >= 0, Nk >= 1 (Nq == 0 or
+ * B == 0: SAMQ_OK, nothing read).  One launch: Nq <= 16 with Nk > 64 splits the keys over the lanes
+ * and waves of a workgroup (exact integer-max / sum combine), everything else runs one lane per
+ * query.  16-byte aligned pointers. */
+int samq_attention_q8_plain(const int8_t* q, const int8_t* k, const int8_t* v, int8_t* out, int B, int Nq,
+                            int Nk, int heads, int hd, float s_q, float s_k, float s_v, float s_a1,
+                            float s_out, hipStream_t stream);
+
+/* The adds between two QActs of the mask decoder (transformer.py:141-142, 339, 347-348, 363-364;
+ * mask_decoder.py:245) on int8 codes: out[i] = q8(fl(a[i] s_a) + fl(b[i % bmod] s_b), s_out) -- two
+ * rounded products and a rounded sum, bit-identical to torch's `x + y` of the two fake-quant f32
+ * tensors followed by UniformQuantizer (quantizer/uniform.py:23-45).  b NULL: out = q8(a s_a, s_out)
+ * (a QAct on a QAct's output, transformer.py:339 qact_pos).  bmod = b's period in elements (the
+ * positional encoding shared over the batch; n when b is not broadcast).  flags: SAMQ_Q_OUT_FQ ->
+ * out is the f32 fake-quant value code * s_out, else int8 codes.  16-byte aligned pointers. */
+int samq_add_q8(const int8_t* a, float s_a, const int8_t* b, float s_b, int64_t bmod, void* out, int64_t n,
+                float s_out, int flags, hipStream_t stream);
+
+/* x = max(x, 0) in place on int8 codes: the ReLU of the decoder's MLPBlock (common.py:65-71 with
+ * act = nn.ReLU, transformer.py:317) after samq_w8a8_gemm's SAMQ_EPI_Q8 -- q8(relu(y), s) ==
+ * max(q8(y, s), 0) exactly.  x 4-byte aligned. */
+int samq_relu_q8(int8_t* x, int64_t n, hipStream_t stream);
+
 /* ---------------------------------------------------------------- patch embedding / neck */
 
 /* PatchEmbed (segment_anything/modeling/image_encoder.py:411-442) + pos_embed add (:108-110)

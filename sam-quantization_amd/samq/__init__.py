@@ -22,12 +22,14 @@ from .modeling import ImageEncoderViT
 from .quant_linear import (QuantLinear, calibrate_act_quant, make_act_quant, make_quant, matmul4,  # noqa: F401
                            triton_matmul4)
 from . import fq_vit  # noqa: F401
+from . import fq_sam  # noqa: F401
+from .fq_sam import build_fq_sam  # noqa: F401
 from .sam_decoder import ResizeLongestSide, SamPredictor, mask_iou  # noqa: F401
 
 __all__ = [
     "load_quant", "autotune_warmup", "QuantLinear", "make_quant", "matmul4", "triton_matmul4",
     "QuantAttention", "make_quant_attn", "ImageEncoderViT", "Sam", "sam_model_registry",
-    "make_act_quant", "calibrate_act_quant", "fq_vit", "SamPredictor", "ResizeLongestSide", "mask_iou",
+    "make_act_quant", "calibrate_act_quant", "fq_vit", "fq_sam", "build_fq_sam", "SamPredictor", "ResizeLongestSide", "mask_iou",
 ]
 
 

@@ -614,3 +614,54 @@ def rel_attention_q8(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], rel_po
         int(nr), _ptr(v16), _stream()), "rel_attention_q8")
     return out
 
+
+
+# ----------------------------------------------------------------------------- mask decoder (fq_vit W8A8)
+def attention_q8_plain(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, s_q: float, s_k: float,
+                       s_v: float, s_a1: float, s_out: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mask decoder's attention on int8 codes (``samq_attention_q8_plain``): q (B, Nq, C), k / v
+    (B, Nk, C) codes of qact1_1 / qact1_2 / qact1_3 -> codes of qact2 (B, Nq, C); C = heads * head_dim."""
+    _need_cuda(q, k, v, out)
+    for t in (q, k, v):
+        assert t.dtype == torch.int8 and t.dim() == 3 and t.is_contiguous()
+    b, nq, c = q.shape
+    nk = k.shape[1]
+    assert k.shape == (b, nk, c) and v.shape == (b, nk, c) and c % heads == 0
+    if out is None:
+        out = torch.empty((b, nq, c), dtype=torch.int8, device=q.device)
+    assert out.dtype == torch.int8 and out.is_contiguous() and out.numel() == b * nq * c
+    _lib.check(_lib.load().samq_attention_q8_plain(_ptr(q), _ptr(k), _ptr(v), _ptr(out), b, nq, nk, heads, c // heads,
+                                                   float(s_q), float(s_k), float(s_v), float(s_a1), float(s_out),
+                                                   _stream()), "attention_q8_plain")
+    return out
+
+
+def add_q8(a: torch.Tensor, s_a: float, b: Optional[torch.Tensor], s_b: float, s_out: float, fake: bool = False,
+           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``q8(a * s_a + b * s_b, s_out)`` on int8 codes (``samq_add_q8``), bit-identical to torch's f32 add of
+    the two fake-quant tensors + UniformQuantizer.  ``b`` None: the requantisation ``q8(a * s_a, s_out)``;
+    a ``b`` with fewer elements is repeated (its numel must divide into whole rows of ``a``: the positional
+    encoding shared over the batch).  ``fake``: f32 ``codes * s_out`` instead of int8 codes."""
+    _need_cuda(a, b, out)
+    assert a.dtype == torch.int8 and a.is_contiguous()
+    n = a.numel()
+    bmod = n
+    if b is not None:
+        assert b.dtype == torch.int8 and b.is_contiguous()
+        bmod = b.numel()
+        assert 0 < bmod <= n and n % bmod == 0 and tuple(b.shape[-1:]) == tuple(a.shape[-1:]), \
+            "add_q8: b must tile a along its leading dims"
+    if out is None:
+        out = torch.empty(a.shape, dtype=torch.float32 if fake else torch.int8, device=a.device)
+    assert out.is_contiguous() and out.numel() == n and out.dtype == (torch.float32 if fake else torch.int8)
+    _lib.check(_lib.load().samq_add_q8(_ptr(a), float(s_a), _ptr(b), float(s_b), bmod, _ptr(out), n, float(s_out),
+                                       _lib.Q_OUT_FQ if fake else 0, _stream()), "add_q8")
+    return out
+
+
+def relu_q8(x: torch.Tensor) -> torch.Tensor:
+    """In-place ``max(codes, 0)`` (``samq_relu_q8``): the ReLU of lin1 -> ReLU -> QAct on ``EPI_Q8`` codes."""
+    _need_cuda(x)
+    assert x.dtype == torch.int8 and x.is_contiguous()
+    _lib.check(_lib.load().samq_relu_q8(_ptr(x), x.numel(), _stream()), "relu_q8")
+    return x

@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Per-click wall time of the fq_vit W8A8 prompt encoder + mask decoder on the GPU.
+
+    python tools/bench_decoder.py [--grid 64] [--clicks 50] [--warmup 10] [--out decoder.jsonl]
+
+One click = ``prompt_encoder`` (one point) + ``mask_decoder`` on a fixed image embedding of a
+``grid`` x ``grid`` map, timed on the host clock between device synchronisations, after warm-up.
+Three paths on the same calibrated model (default initialisation, minmax calibration on three random sets):
+
+* ``graph``   the decoder engine replaying its captured HIP graph;
+* ``eager``   the decoder engine launching its kernels one by one;
+* ``modules`` the module graph of the same model on the GPU (``mask_decoder.use_engine = False``).
+
+Also counted: the kernel launches of one transformer forward on each path (torch profiler), and the
+launches of the module-graph tail (upscaling, hypernetwork MLPs, IoU head) that runs after the engine.
+One JSON line per path.
+"""
+import argparse
+import json
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "sam-quantization_amd"))
+
+import torch  # noqa: E402
+
+
+def build(grid, seed=0):
+    """The prompt encoder + mask decoder at their default initialisation (torch seed ``seed``), minmax
+    calibration on three random (image embedding, point) sets, quant mode; a fourth set to time."""
+    from samq import fq_sam
+    torch.manual_seed(seed)
+    img = grid * 16
+    pe, md = fq_sam.build_fq_prompt_decoder(image_size=img)
+    pe, md = pe.cuda().eval(), md.cuda().eval()
+    qm = [m for mod in (pe, md) for m in mod.modules()
+          if type(m) in (fq_sam.QConv2d, fq_sam.QLinear, fq_sam.QAct, fq_sam.QIntSoftmax)]
+    g = torch.Generator(device="cpu").manual_seed(seed + 1)
+
+    def inputs():
+        emb = torch.randn((1, 256, grid, grid), generator=g).cuda()
+        pt = (torch.rand((1, 1, 2), generator=g) * img).cuda()
+        return emb, (pt, torch.ones((1, 1), dtype=torch.int32).cuda())
+    with torch.no_grad():
+        for m in qm:
+            m.calibrate = True
+        md.refresh()
+        for i in range(3):
+            if i == 2:
+                for m in qm:
+                    m.last_calibrate = True
+            emb, pts = inputs()
+            sparse, dense = pe(points=pts, boxes=None, masks=None)
+            md.predict_masks(emb, pe.get_dense_pe(), sparse, dense)
+        for m in qm:
+            m.calibrate = False
+            m.quant = True
+        md.refresh()   # the flags were set by hand
+    return pe, md, inputs()
+
+
+def launches(fn):
+    """Kernel launches (and memsets / copies) of one call, from the torch profiler; None without one."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    try:
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(e.count for e in prof.key_averages() if e.device_type == torch.autograd.DeviceType.CUDA)
+    except Exception as e:   # no profiler on this build: the times are still reported
+        print(f"launch count unavailable: {e}", file=sys.stderr)
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", type=int, default=64)
+    ap.add_argument("--clicks", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    pe, md, (emb, pts) = build(args.grid)
+    eng = md.engine()
+    dense_pe = pe.get_dense_pe()
+
+    @torch.no_grad()
+    def click():
+        sparse, dense = pe(points=pts, boxes=None, masks=None)
+        return md(emb, dense_pe, sparse, dense, True)
+
+    try:
+        head = subprocess.run(["git", "-C", str(REPO), "rev-parse", "--short", "HEAD"], capture_output=True,
+                              text=True).stdout.strip()
+    except OSError:
+        head = ""
+    base = dict(grid=args.grid, clicks=args.clicks, device=torch.cuda.get_device_name(0), build=head,
+                torch=torch.__version__)
+    for path in ("graph", "eager", "modules"):
+        md.use_engine = path != "modules"
+        eng.drop_graphs()
+        click()
+        if path == "graph":
+            eng.capture(5 + 2)
+        for _ in range(args.warmup):
+            click()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.clicks):
+            t0 = time.perf_counter()
+            click()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        times.sort()
+        rec = dict(base, path=path, ms_median=1e3 * times[len(times) // 2], ms_min=1e3 * times[0],
+                   ms_p90=1e3 * times[int(0.9 * (len(times) - 1))])
+        if path != "graph":   # a replayed graph shows as one launch; its kernels are the eager engine's
+            rec["launches_per_click"] = launches(click)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+    md.use_engine = True
+    # the parts of one eager click: prompt encoder, engine (transformer), module-graph tail
+    with torch.no_grad():
+        sparse, dense = pe(points=pts, boxes=None, masks=None)
+        tokens = torch.cat([md.iou_token.weight, md.mask_tokens.weight, sparse[0]], dim=0)[None].contiguous()
+        hs, src = eng.forward(emb, dense, dense_pe, tokens)
+        shape = (1, emb.shape[1], args.grid, args.grid)
+        parts = dict(path="launch_split",
+                     prompt_encoder=launches(lambda: pe(points=pts, boxes=None, masks=None)),
+                     engine=launches(lambda: eng.forward(emb, dense, dense_pe, tokens)),
+                     tail=launches(lambda: md.heads_forward(hs, src, shape)))
+    print(json.dumps(dict(base, **parts)), flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(json.dumps(dict(base, **parts)) + "\n")
+
+
+if __name__ == "__main__":
+    main()
