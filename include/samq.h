@@ -414,6 +414,52 @@ int samq_add_q8(const int8_t* a, float s_a, const int8_t* b, float s_b, int64_t 
  * max(q8(y, s), 0) exactly.  x 4-byte aligned. */
 int samq_relu_q8(int8_t* x, int64_t n, hipStream_t stream);
 
+/* ---- the mask decoder's tail (mask_decoder.py:251-279) on int8 codes: three launches.
+ * ConvTranspose2d(k2 s2) weights stay float (QConvTranspose2d is outside the Sam switches): the
+ * fp32 weight [Cin, Cout, 2, 2] is passed as W[n][k] = weight[k][co][kh][kw], n = (2 kh + kw) Cout + co,
+ * split w = hi + lo 2^-11 (hi = fp16(w), lo = fp16((w - hi) 2^11)) into two fp16 planes, each in MFMA
+ * fragment order: [4 Cout / 32][Cin / 16][64 lanes][8], lane = 32 khalf + nn holds
+ * W[32 tile + nn][16 kstep + 8 khalf + 0..7] (ops.convt_split_weight builds them).  All QActs
+ * layer-wise, zero point 0.  Empty shapes: SAMQ_OK, nothing read.  16-byte aligned pointers. */
+
+/* output_upscaling[0..2] + qacts[0..2]: x int8 [B*h*w, Cin] token rows (the transformer's keys, s_in)
+ *   c0 = q8(s_in * sum_k x w + bias, s0)                       (qacts[0]; fp32-level sum)
+ *   c1 = q8(LayerNorm2D over the 64 channels of (c0 s0), s1)    (two-pass fp32 statistics, eps)
+ *   out int8 [B, 2h, 2w, 64] (NHWC) = q8(gelu_erf(c1 s1), s2)   (qacts[2])
+ * dbg_q0 / dbg_q1 (optional, NULL to skip): the codes c0 / c1 in out's layout.  Cout == 64,
+ * Cin % 16 == 0 (else SAMQ_ERR_UNSUPPORTED); any B, h, w >= 0. */
+int samq_upscale0_q8(const int8_t* x, const void* w_hi, const void* w_lo, const float* bias, const float* gamma,
+                     const float* beta, int8_t* out, int8_t* dbg_q0, int8_t* dbg_q1, int B, int h, int w, int Cin,
+                     int Cout, float eps, float s_in, float s0, float s1, float s2, hipStream_t stream);
+
+/* The hypernetwork MLPs and the IoU head (mask_decoder.py:284-362, bare QLinears: one weight scale
+ * each) in one launch: MLP j < n_hyper on token 1 + j of q int8 [B, Nt, C] (the transformer's qact4,
+ * s_in), MLP n_hyper (the IoU head) on token 0.  w1 [n_hyper + 1][C/4][Hd][4], w2 [..][Hd/4][Hd][4],
+ * w3 [..][Hd/4][NO][4] int8 weight codes (4 consecutive k of an output column together; NO =
+ * max(no_hyper, no_iou), unused columns zero), b1 / b2 [..][Hd], b3 [..][NO] f32, scales [..][8] f32 =
+ * s_w1, s_w2, s_w3, qacts1[0], qacts2[0], qacts1[1], qacts2[1], qact3.  Hidden layer, both quantisers:
+ *   c1 = q8(float(sum x w) (s_x s_w) + bias, s1); r = max(c1, 0); c2 = q8(r s1, s2)  (r when s1 == s2)
+ * -- bit-identical to samq_w8a8_gemm(SAMQ_EPI_Q8) -> samq_relu_q8 -> samq_add_q8; last layer
+ * q8(.., qact3).  hyper int8 [B, n_hyper, no_hyper] codes; iou f32 [B, no_iou] = code * s3.  dbg
+ * (optional) int8 [B, n_hyper + 1, 4, Hd]: c1, c2 of both hidden layers.  C % 4 == 0, C <= 1024,
+ * Hd % 4 == 0, Hd <= 256, outputs <= 256 (else SAMQ_ERR_UNSUPPORTED); Nt >= 1 + n_hyper. */
+int samq_decoder_mlps_q8(const int8_t* q, const void* w1, const void* w2, const void* w3, const float* b1,
+                         const float* b2, const float* b3, const float* scales, int8_t* hyper, float* iou,
+                         int8_t* dbg, int B, int Nt, int C, int Hd, int n_hyper, int no_hyper, int no_iou,
+                         float s_in, hipStream_t stream);
+
+/* output_upscaling[3..4] + qacts[3..4], the mask product and the decoder's qact1: x int8
+ * [B, H, W, Cin] (NHWC: samq_upscale0_q8's out, s_in), hyper int8 [B, n_masks, 32] with scales
+ * s_hyper f32 [n_masks] (device memory):
+ *   c3 = q8(s_in * sum_k x w + bias, s3);  c4 = q8(gelu_erf(c3 s3), s4)       [B, 2H, 2W, 32]
+ *   masks f32 [B, n_masks, 2H, 2W] = q8(float(sum_c hyper c4) (s_hyper[m] s4), s_q1) * s_q1
+ * (the sum an exact int32 dot).  dbg_q3 / x4 (optional): the codes c3 / c4, NHWC.  Cout == 32,
+ * Cin % 16 == 0 (else SAMQ_ERR_UNSUPPORTED). */
+int samq_upscale1_masks_q8(const int8_t* x, const void* w_hi, const void* w_lo, const float* bias,
+                           const int8_t* hyper, const float* s_hyper, float* masks, int8_t* dbg_q3, int8_t* x4,
+                           int B, int H, int W, int Cin, int Cout, int n_masks, float s_in, float s3, float s4,
+                           float s_q1, hipStream_t stream);
+
 /* ---------------------------------------------------------------- patch embedding / neck */
 
 /* PatchEmbed (segment_anything/modeling/image_encoder.py:411-442) + pos_embed add (:108-110)

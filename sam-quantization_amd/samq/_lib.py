@@ -103,6 +103,12 @@ SIGNATURES = {
                                        _vp]),
     "samq_add_q8": (_i32, [_vp, _f32, _vp, _f32, _i64, _vp, _i64, _f32, _i32, _vp]),
     "samq_relu_q8": (_i32, [_vp, _i64, _vp]),
+    "samq_upscale0_q8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
+                                _f32, _f32, _f32, _vp]),
+    "samq_decoder_mlps_q8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                    _i32, _i32, _i32, _f32, _vp]),
+    "samq_upscale1_masks_q8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                      _f32, _f32, _f32, _f32, _vp]),
     "samq_patch_embed": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "samq_patch_embed_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "samq_patch_embed_u8": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32,

@@ -26,9 +26,11 @@ Quirks of the reference kept as they are (``tests/golden/fq_decoder.npz`` pins t
 
 Supported configuration as for the encoder: ``Config(False, False, m)`` with ``BIT_TYPE_A = int8``.
 Float / calibration forwards and the CPU run the module graph with torch ops.  In quant mode on a
-GPU ``MaskDecoder.predict_masks`` runs the transformer through ``W8A8DecoderEngine`` (int8 codes
-between HIP kernels, one HIP graph per token count); the prompt encoder, the output upscaling, the
-hypernetwork MLPs and the IoU head stay the module graph with the HIP fake-quant ``QAct``.
+GPU ``MaskDecoder.predict_masks`` runs through ``W8A8DecoderEngine``: int8 codes between HIP kernels
+from ``qact_embed1`` to the low-res masks and ``iou_pred`` (the two-way transformer, then three
+kernels for the output upscaling, the hypernetwork MLPs, the IoU head and the mask product), one
+HIP graph per token count.  ``use_fused_tail = False`` keeps the module graph (``heads_forward``,
+HIP fake-quant ``QAct``) behind the transformer; the prompt encoder is the module graph.
 """
 from __future__ import annotations
 
@@ -316,6 +318,7 @@ class MaskDecoder(nn.Module):
         self.iou_prediction_head = MLP(transformer_dim, iou_head_hidden_dim, self.num_mask_tokens, iou_head_depth,
                                        quant=quant, calibrate=calibrate, cfg=cfg)
         self.use_engine = True   # False: the module graph on the GPU too (tools/bench_decoder.py)
+        self.use_fused_tail = True   # False: the engine's transformer, then heads_forward (the module-graph tail)
         self._engine = None
 
     def _qmods(self):
@@ -358,11 +361,20 @@ class MaskDecoder(nn.Module):
                       taps: Optional[dict] = None):
         """``taps`` (tests): the fake-quant f32 values of ``qact_embed1`` / ``qact_embed2`` /
         ``pos_src_qact``, every block's ``layers.<i>.queries`` / ``.keys``, the transformer's
-        ``queries`` / ``keys`` and the low-res masks ``qact1``."""
+        ``queries`` / ``keys`` and the low-res masks ``qact1``; through the engine's fused tail also
+        ``upscaling.qacts.0`` .. ``.4`` and ``hyper_in``.
+
+        Through the fused tail, once ``engine().capture(n_tokens)`` has recorded a graph for this token
+        count, ``masks`` / ``iou_pred`` (and the slices ``forward`` returns) are the graph's own output
+        buffers: the next click of that token count overwrites them -- clone what must outlive it (a
+        low-res mask fed back as the next click's mask input).  Without a captured graph they are fresh."""
         output_tokens = torch.cat([self.iou_token.weight, self.mask_tokens.weight], dim=0)
         output_tokens = output_tokens.unsqueeze(0).expand(sparse_prompt_embeddings.size(0), -1, -1)
         raw_tokens = torch.cat((output_tokens, sparse_prompt_embeddings), dim=1)
         if self.use_engine and raw_tokens.is_cuda and self.is_quant():
+            if self.use_fused_tail:
+                return self.engine().forward_masks(image_embeddings, dense_prompt_embeddings, image_pe, raw_tokens,
+                                                   taps=taps)
             hs, src = self.engine().forward(image_embeddings, dense_prompt_embeddings, image_pe, raw_tokens, taps=taps)
             b, c, h, w = src.shape[0], image_embeddings.shape[1], image_embeddings.shape[2], image_embeddings.shape[3]
         else:
@@ -487,12 +499,22 @@ class W8A8DecoderEngine:
     adds (qact4, qact5) -> 3 GEMMs -> attention -> out_proj + residual + qact6 -> LN + qact7 |
     lin1 GEMM + mlp.qact1, ReLU -> lin2 GEMM + mlp.qact2 (= qact8) + residual + qact9 -> LN + qact10 |
     adds (qact11, qact12) -> 3 GEMMs -> attention (image queries) -> out_proj + residual + qact13 ->
-    LN + qact14.  Then the final token-to-image attention the same way and LN + qact4 -> f32.
+    LN + qact14.  Then the final token-to-image attention the same way and LN + qact4 -> f32
+    (``forward``) or int8 codes (``forward_masks``).
+
+    ``forward_masks`` goes on to the masks in three more kernels (``csrc/decoder_tail.hip``):
+    ``upscale0_q8`` (convT 256 -> 64, qacts[0], LayerNorm2D, qacts[1], GELU, qacts[2]) on the key codes,
+    ``decoder_mlps_q8`` (the four hypernetwork MLPs and the IoU head) on the query codes and
+    ``upscale1_masks_q8`` (convT 64 -> 32, qacts[3], GELU, qacts[4], hyper_in @ x, qact1).  The tail's
+    weights are a snapshot too: the float transposed-convolution weights split into two fp16 planes,
+    the MLP weight codes quantised once.
 
     The image side (``qact_embed2(image_embeddings + dense)`` and ``pos_src_qact(image_pe)`` as token
     rows of codes) is quantised once per image and cached; a forward quantises the prompt tokens
     and runs the kernels.  No host synchronisation in ``forward``; ``capture(n_tokens)`` records it
-    into one HIP graph per token count.
+    into HIP graphs, two per token count: one that ends in the f32 ``queries`` / ``keys`` (``forward``) and
+    one that ends in ``masks`` / ``iou_pred`` (``forward_masks``) -- a click replays the second only and
+    does not pay for the f32 outputs it does not read.
     """
 
     def __init__(self, dec: MaskDecoder):
@@ -523,6 +545,10 @@ class W8A8DecoderEngine:
         self.final = self._attn(tr.final_attn_token_to_image)
         self.norm_final = self._norm(tr.norm_final_attn)
         self.sf = [None] + [_s(getattr(tr, f"qact{i}")) for i in range(1, 5)]
+        # the tail's snapshot: now when the decoder uses it -- an unsupported tail (sigmoid_output, a
+        # per-channel tail QAct) is refused here, also for callers of forward() alone: set
+        # use_fused_tail = False before engine() to run such a decoder -- else on the first forward_masks
+        self._tail = self._snapshot_tail() if dec.use_fused_tail else None
         self._image = None      # (image_embeddings, dense, image_pe, their versions) -> cached codes
         self._graphs = {}       # (n_tokens, batch, hw) -> (graph, static tokens, outputs)
         self.forwards = 0       # engine forwards (eager or replayed); the tests' "the engine ran" counter
@@ -550,6 +576,60 @@ class W8A8DecoderEngine:
     @staticmethod
     def _norm(n):
         return n.weight.detach().float().contiguous(), n.bias.detach().float().contiguous(), n.eps
+
+    def _snapshot_tail(self):
+        """Output upscaling, hypernetwork MLPs and IoU head for the three tail kernels."""
+        ops, dec, dev = self.ops, self.dec, self.dev
+        up = dec.output_upscaling
+        if not (len(up) == 5 and isinstance(up[0], QConvTranspose2d) and isinstance(up[1], QIntLayerNorm2D)
+                and isinstance(up[3], QConvTranspose2d) and all(isinstance(up[i], nn.GELU) for i in (2, 4))
+                and all(getattr(up[i], "approximate", "none") == "none" for i in (2, 4))):
+            raise NotImplementedError("W8A8 decoder tail: output_upscaling must be convT, LayerNorm2D, GELU, convT, GELU")
+
+        def convt(m):
+            if (tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.output_padding), tuple(m.dilation),
+                    m.groups) != ((2, 2), (2, 2), (0, 0), (0, 0), (1, 1), 1):
+                raise NotImplementedError("W8A8 decoder tail: transposed convolutions must be kernel 2, stride 2")
+            w = (m.quantizer(m.weight) if m.quant else m.weight).detach().float()   # float unless set by hand
+            hi, lo = ops.convt_split_weight(w)
+            bias = torch.zeros(w.shape[1], device=dev) if m.bias is None else m.bias.detach().float().contiguous()
+            return dict(hi=hi, lo=lo, bias=bias, cin=w.shape[0], cout=w.shape[1])
+        mlps = list(dec.output_hypernetworks_mlps) + [dec.iou_prediction_head]
+        if any(m.num_layers != 3 for m in mlps):
+            raise NotImplementedError("W8A8 decoder tail: 3-layer MLPs (iou_head_depth = 3)")
+        hid, cin = mlps[0].layers[1].in_features, mlps[0].layers[0].in_features
+        no_h, no_i = mlps[0].layers[2].out_features, mlps[-1].layers[2].out_features
+        no = max(no_h, no_i)
+        w1, w2, w3, b1, b2, b3, sc = [], [], [], [], [], [], []
+        for i, m in enumerate(mlps):
+            if m.sigmoid_output:
+                raise NotImplementedError("W8A8 decoder tail: MLP(sigmoid_output=True) is not supported")
+            want = [(cin, hid), (hid, hid), (hid, no_i if i == len(mlps) - 1 else no_h)]
+            if [(l.in_features, l.out_features) for l in m.layers] != want:
+                raise NotImplementedError("W8A8 decoder tail: MLPs of one input / hidden width")
+            ws = []
+            for lay, dst, bdst, pad in zip(m.layers, (w1, w2, w3), (b1, b2, b3), (0, 0, no)):
+                s = lay.quantizer.scale
+                if s is None:
+                    raise RuntimeError("fq_vit: weight quantizer is not calibrated")
+                if s.numel() != 1:
+                    raise NotImplementedError("W8A8 decoder tail: the MLPs' QLinears have one weight scale each")
+                w = lay.weight.detach().float()
+                s = s.detach().float().reshape(-1).to(w.device)   # the rounding of _weight
+                codes = torch.clamp(torch.round((w.double() / s.double()[:, None]).float()), -128, 127).to(torch.int8)
+                dst.append(ops.mlp_pack_weight(codes, pad))
+                bias = torch.zeros(w.shape[0], device=dev) if lay.bias is None else lay.bias.detach().float()
+                bdst.append(F.pad(bias, (0, max(pad, w.shape[0]) - w.shape[0])))
+                ws.append(float(s[0]))
+            sc.append(ws + [_s(m.qacts1[0]), _s(m.qacts2[0]), _s(m.qacts1[1]), _s(m.qacts2[1]), _s(m.qact3)])
+        ln = up[1]
+        return dict(up0=convt(up[0]), up1=convt(up[3]), gamma=ln.weight.detach().float().contiguous(),
+                    beta=ln.bias.detach().float().contiguous(), eps=ln.eps, su=[_s(q) for q in dec.qacts],
+                    s_q1=_s(dec.qact1), w1=torch.stack(w1), w2=torch.stack(w2), w3=torch.stack(w3),
+                    b1=torch.stack(b1).contiguous(), b2=torch.stack(b2).contiguous(), b3=torch.stack(b3).contiguous(),
+                    scales=torch.tensor(sc, dtype=torch.float32, device=dev),
+                    s_hyper=torch.tensor([r[7] for r in sc[:-1]], dtype=torch.float32, device=dev),
+                    s_hyper_host=[r[7] for r in sc[:-1]], n_hyper=len(mlps) - 1, no_h=no_h, no_i=no_i)
 
     def _gemm(self, a, lw, epi, a_scale, out_scale, mid=0.0, res=None, res_scale=0.0, out=None):
         return self.ops.w8a8_gemm(a, lw["packed"], lw["scale"], lw["n"], lw["bias"], epi, a_scale, out_scale, mid,
@@ -610,6 +690,26 @@ class W8A8DecoderEngine:
 
     __call__ = forward
 
+    @torch.no_grad()
+    def forward_masks(self, image_embeddings, dense, image_pe, raw_tokens, taps: Optional[dict] = None):
+        """The whole decoder behind the prompt encoder: ``(masks, iou_pred)`` -- the fake-quant f32 low-res
+        masks (B, 4, 4h, 4w) of ``qact1`` and the IoU head's (B, 4) -- from the same inputs as ``forward``.
+        The transformer's ``qact4`` and the keys stay int8 codes; three tail kernels follow on the same
+        stream.  Replays the captured graph of this token count if there is one (and no ``taps``): the
+        two tensors are then the graph's own buffers, overwritten by the next replay.  ``taps`` also
+        receives ``upscaling.qacts.0`` .. ``.4`` (NCHW), ``hyper_in`` and ``qact1``."""
+        img = self.set_image(image_embeddings, dense, image_pe)
+        b, nt, c = raw_tokens.shape
+        if b != img["b"]:
+            raise ValueError(f"W8A8 decoder engine: {b} prompt sets for {img['b']} image-side batches")
+        self.forwards += 1
+        g = self._graphs.get((nt, b, img["hw"])) if taps is None else None
+        if g is not None and g["src"] is img["src"] and g.get("graph_masks") is not None:
+            g["tokens"].copy_(raw_tokens)
+            g["graph_masks"].replay()
+            return g["masks"], g["iou_pred"]
+        return self._run(raw_tokens.float().contiguous(), img, taps, tail=True)
+
     def _attention(self, a, q_in, s_qin, k_in, s_kin, v_in, s_vin, b):
         """q / k / v projections + attention: codes of attn.qact2 (rows of q_in, internal dim)."""
         ops = self.ops
@@ -620,7 +720,34 @@ class W8A8DecoderEngine:
         return ops.attention_q8_plain(q.view(b, -1, d), k.view(b, -1, d), v.view(b, -1, d), a["heads"], a["s_q"],
                                       a["s_k"], a["s_v"], a["s_a1"], a["s_ao"]).view(-1, d)
 
-    def _run(self, raw_tokens, img, taps):
+    def _tail_run(self, qc, K, s_K, s_q, img, taps):
+        """The three tail kernels: query codes (B, Nt, C) of qact4, key codes (B * hw, C) -> masks, iou_pred."""
+        ops = self.ops
+        if self._tail is None:
+            self._tail = self._snapshot_tail()
+        t = self._tail
+        b = qc.shape[0]
+        h, w = img["grid"]
+        u0, u1, su = t["up0"], t["up1"], t["su"]
+        dbg = None
+        if taps is not None:
+            i8 = lambda ch, k: torch.empty((b, k * h, k * w, ch), dtype=torch.int8, device=self.dev)
+            dbg = [i8(u0["cout"], 2), i8(u0["cout"], 2), None, i8(u1["cout"], 4), i8(u1["cout"], 4)]
+        x2 = ops.upscale0_q8(K, u0["hi"], u0["lo"], u0["bias"], t["gamma"], t["beta"], t["eps"], b, h, w, s_K,
+                             su[0], su[1], su[2], dbg_q0=dbg and dbg[0], dbg_q1=dbg and dbg[1])
+        hyper, iou = ops.decoder_mlps_q8(qc, t["w1"], t["w2"], t["w3"], t["b1"], t["b2"], t["b3"], t["scales"],
+                                         t["n_hyper"], t["no_h"], t["no_i"], s_q)
+        masks = ops.upscale1_masks_q8(x2, u1["hi"], u1["lo"], u1["bias"], hyper, t["s_hyper"], su[2], su[3], su[4],
+                                      t["s_q1"], dbg_q3=dbg and dbg[3], x4=dbg and dbg[4])
+        if taps is not None:
+            dbg[2] = x2
+            for i, codes in enumerate(dbg):   # NCHW fake-quant values, as the module graph's
+                taps[f"upscaling.qacts.{i}"] = codes.permute(0, 3, 1, 2).float() * su[i]
+            taps["hyper_in"] = hyper.float() * t["s_hyper"][None, :, None]
+            taps["qact1"] = masks
+        return masks, iou
+
+    def _run(self, raw_tokens, img, taps, tail=False):
         ops = self.ops
         b, nt, c = raw_tokens.shape
         hw = img["hw"]
@@ -706,6 +833,11 @@ class W8A8DecoderEngine:
         o = self._attention(a, qin, sf[1], kin, sf[2], K, s_K, b)
         Q = self._gemm(o, a["o"], ops.EPI_Q8_RES, a["s_ao"], sf[3], mid=a["s_o"], res=Q, res_scale=s_Q)
         tap("transformer.qact3", Q, sf[3], nt)
+        if tail:   # qact4 and the keys stay codes; no f32 pass over the keys
+            qc = ops.layernorm_q(Q, *self.norm_final, in_scale=sf[3], out_scale=sf[4]).view(b, nt, c)
+            if taps is not None:
+                taps["queries"], taps["keys"] = qc.float() * sf[4], K.view(b, hw, c).float() * s_K
+            return self._tail_run(qc, K, s_K, sf[4], img, taps)
         queries = ops.layernorm_q(Q, *self.norm_final, in_scale=sf[3], out_scale=sf[4],
                                   out_dtype=torch.float32).view(b, nt, c)
         keys = ops.add_q8(K, s_K, None, 0.0, s_K, fake=True).view(b, hw, c)   # codes * scale as f32
@@ -715,8 +847,14 @@ class W8A8DecoderEngine:
 
     # -- HIP graph
     def capture(self, n_tokens: int, image_embeddings=None, dense=None, image_pe=None):
-        """Record the forward for ``n_tokens`` tokens (5 + prompt points) on the current image into a
-        HIP graph; ``forward`` then replays it for that token count while the image stays cached.
+        """Record the forward for ``n_tokens`` tokens (5 + prompt points) on the current image into HIP
+        graphs; ``forward`` / ``forward_masks`` then replay them for that token count while the image stays
+        cached.  Two graphs on one static token buffer: the transformer with its f32 ``queries`` / ``keys``
+        (returned) and, when the decoder uses the fused tail, the whole click to ``masks`` / ``iou_pred``.
+        One graph for both would make every click compute and store the f32 queries / keys (a pass over
+        B * hw * C floats) that only ``forward``'s callers read.  ``use_fused_tail`` is read here: captured
+        while it is False, the entry has no masks graph and ``forward_masks`` for that token count runs its
+        kernels eagerly until ``capture`` is called again.
         Call after a ``forward`` (or with the image tensors) so the image side is quantised."""
         if image_embeddings is not None:
             self.set_image(image_embeddings, dense, image_pe)
@@ -734,7 +872,18 @@ class W8A8DecoderEngine:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             out = self._run(tokens, img, None)
-        self._graphs[(n_tokens, b, hw)] = dict(graph=graph, tokens=tokens, out=out, src=img["src"])
+        entry = dict(graph=graph, tokens=tokens, out=out, src=img["src"], graph_masks=None)
+        if self.dec.use_fused_tail:
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    self._run(tokens, img, None, tail=True)
+            torch.cuda.current_stream().wait_stream(s)
+            gm = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gm):
+                entry["masks"], entry["iou_pred"] = self._run(tokens, img, None, tail=True)
+            entry["graph_masks"] = gm
+        self._graphs[(n_tokens, b, hw)] = entry
         return graph
 
     def drop_graphs(self):

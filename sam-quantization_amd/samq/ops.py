@@ -665,3 +665,114 @@ def relu_q8(x: torch.Tensor) -> torch.Tensor:
     assert x.dtype == torch.int8 and x.is_contiguous()
     _lib.check(_lib.load().samq_relu_q8(_ptr(x), x.numel(), _stream()), "relu_q8")
     return x
+
+
+# ----------------------------------------------------------------------------- mask decoder tail (fq_vit W8A8)
+def convt_split_weight(weight: torch.Tensor):
+    """A ``ConvTranspose2d(k2 s2)`` fp32 weight [Cin, Cout, 2, 2] -> the (hi, lo) fp16 planes the tail
+    kernels read: the GEMM matrix W[n][k] = weight[k][co][kh][kw], n = (2 kh + kw) Cout + co, split
+    w = hi + lo 2^-11 and put in MFMA fragment order [4 Cout / 32][Cin / 16][64][8]."""
+    cin, cout, kh, kw = weight.shape
+    assert (kh, kw) == (2, 2) and cin % 16 == 0 and (4 * cout) % 32 == 0
+    w = weight.detach().float().permute(2, 3, 1, 0).reshape(4 * cout, cin)
+    hi = w.to(torch.float16)
+    lo = ((w - hi.float()) * 2048.0).to(torch.float16)
+
+    def frag(p):   # [N, K] -> [N/32, K/16, khalf, n, 8]: lane = 32 khalf + n
+        return p.reshape(4 * cout // 32, 32, cin // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().reshape(-1)
+    return frag(hi), frag(lo)
+
+
+def mlp_pack_weight(codes: torch.Tensor, n_pad: int = 0) -> torch.Tensor:
+    """int8 weight codes [N, K] of a QLinear -> ``samq_decoder_mlps_q8``'s [K/4][max(N, n_pad)][4]
+    (4 consecutive k of an output column in one dword; columns past N zero)."""
+    n, k = codes.shape
+    assert codes.dtype == torch.int8 and k % 4 == 0
+    if n_pad > n:
+        codes = torch.cat([codes, codes.new_zeros((n_pad - n, k))])
+    return codes.reshape(codes.shape[0], k // 4, 4).permute(1, 0, 2).contiguous()
+
+
+def upscale0_q8(x: torch.Tensor, w_hi: torch.Tensor, w_lo: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor,
+                beta: torch.Tensor, eps: float, b: int, h: int, w: int, s_in: float, s0: float, s1: float, s2: float,
+                out: Optional[torch.Tensor] = None, dbg_q0: Optional[torch.Tensor] = None,
+                dbg_q1: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``samq_upscale0_q8``: key codes (b*h*w, Cin) -> codes of ``qacts[2]`` (b, 2h, 2w, Cout) NHWC;
+    ``dbg_q0`` / ``dbg_q1`` (int8, out's shape) receive the codes of ``qacts[0]`` / ``qacts[1]``."""
+    _need_cuda(x, w_hi, w_lo, bias, gamma, beta, out, dbg_q0, dbg_q1)
+    cout = bias.numel()
+    cin = x.shape[-1]
+    assert x.dtype == torch.int8 and x.is_contiguous() and x.numel() == b * h * w * cin
+    assert w_hi.dtype == torch.float16 and w_lo.dtype == torch.float16
+    assert w_hi.numel() == 4 * cout * cin and w_lo.numel() == 4 * cout * cin
+    for t in (bias, gamma, beta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == cout
+    if out is None:
+        out = torch.empty((b, 2 * h, 2 * w, cout), dtype=torch.int8, device=x.device)
+    for t in (out, dbg_q0, dbg_q1):
+        assert t is None or (t.dtype == torch.int8 and t.is_contiguous() and t.numel() == b * 4 * h * w * cout)
+    _lib.check(_lib.load().samq_upscale0_q8(_ptr(x), _ptr(w_hi), _ptr(w_lo), _ptr(bias), _ptr(gamma), _ptr(beta),
+                                            _ptr(out), _ptr(dbg_q0), _ptr(dbg_q1), b, h, w, cin, cout, float(eps),
+                                            float(s_in), float(s0), float(s1), float(s2), _stream()), "upscale0_q8")
+    return out
+
+
+def decoder_mlps_q8(q: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, w3: torch.Tensor, b1: torch.Tensor,
+                    b2: torch.Tensor, b3: torch.Tensor, scales: torch.Tensor, n_hyper: int, no_hyper: int, no_iou: int,
+                    s_in: float, hyper: Optional[torch.Tensor] = None, iou: Optional[torch.Tensor] = None,
+                    dbg: Optional[torch.Tensor] = None):
+    """``samq_decoder_mlps_q8``: q (B, Nt, C) codes of the transformer's ``qact4`` -> (hyper codes
+    (B, n_hyper, no_hyper) int8, iou_pred (B, no_iou) f32).  Weights from ``mlp_pack_weight`` stacked
+    over the n_hyper + 1 MLPs (the IoU head last); ``scales`` (n_hyper + 1, 8) f32 on the device."""
+    _need_cuda(q, w1, w2, w3, b1, b2, b3, scales, hyper, iou, dbg)
+    assert q.dtype == torch.int8 and q.dim() == 3 and q.is_contiguous()
+    b, nt, c = q.shape
+    nm = n_hyper + 1
+    hd = w2.shape[-2]
+    no = max(no_hyper, no_iou)
+    assert all(t.dtype == torch.int8 and t.is_contiguous() for t in (w1, w2, w3))
+    assert tuple(w1.shape) == (nm, c // 4, hd, 4) and tuple(w2.shape) == (nm, hd // 4, hd, 4)
+    assert tuple(w3.shape) == (nm, hd // 4, no, 4)
+    for t, shp in ((b1, (nm, hd)), (b2, (nm, hd)), (b3, (nm, no)), (scales, (nm, 8))):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shp
+    if hyper is None:
+        hyper = torch.empty((b, n_hyper, no_hyper), dtype=torch.int8, device=q.device)
+    if iou is None:
+        iou = torch.empty((b, no_iou), dtype=torch.float32, device=q.device)
+    assert hyper.dtype == torch.int8 and hyper.is_contiguous() and hyper.numel() == b * n_hyper * no_hyper
+    assert iou.dtype == torch.float32 and iou.is_contiguous() and iou.numel() == b * no_iou
+    assert dbg is None or (dbg.dtype == torch.int8 and dbg.is_contiguous() and dbg.numel() == b * nm * 4 * hd)
+    _lib.check(_lib.load().samq_decoder_mlps_q8(_ptr(q), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(b1), _ptr(b2), _ptr(b3),
+                                                _ptr(scales), _ptr(hyper), _ptr(iou), _ptr(dbg), b, nt, c, hd, n_hyper,
+                                                no_hyper, no_iou, float(s_in), _stream()), "decoder_mlps_q8")
+    return hyper, iou
+
+
+def upscale1_masks_q8(x: torch.Tensor, w_hi: torch.Tensor, w_lo: torch.Tensor, bias: torch.Tensor,
+                      hyper: torch.Tensor, s_hyper: torch.Tensor, s_in: float, s3: float, s4: float, s_q1: float,
+                      masks: Optional[torch.Tensor] = None, dbg_q3: Optional[torch.Tensor] = None,
+                      x4: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``samq_upscale1_masks_q8``: x (B, H, W, Cin) NHWC codes of ``qacts[2]``, hyper (B, M, Cout) codes
+    with scales ``s_hyper`` (M,) f32 on the device -> masks (B, M, 2H, 2W) fake-quant f32 (``qact1``);
+    ``dbg_q3`` / ``x4`` (int8 (B, 2H, 2W, Cout)) receive the codes of ``qacts[3]`` / ``qacts[4]``."""
+    _need_cuda(x, w_hi, w_lo, bias, hyper, s_hyper, masks, dbg_q3, x4)
+    assert x.dtype == torch.int8 and x.dim() == 4 and x.is_contiguous()
+    b, hh, ww, cin = x.shape
+    cout = bias.numel()
+    assert w_hi.dtype == torch.float16 and w_lo.dtype == torch.float16
+    assert w_hi.numel() == 4 * cout * cin and w_lo.numel() == 4 * cout * cin
+    assert bias.dtype == torch.float32 and bias.is_contiguous()
+    assert hyper.dtype == torch.int8 and hyper.dim() == 3 and hyper.is_contiguous()
+    nm = hyper.shape[1]
+    assert tuple(hyper.shape) == (b, nm, cout), "upscale1_masks_q8: hyper must be (B, masks, Cout)"
+    assert s_hyper.dtype == torch.float32 and s_hyper.is_contiguous() and s_hyper.numel() == nm
+    if masks is None:
+        masks = torch.empty((b, nm, 2 * hh, 2 * ww), dtype=torch.float32, device=x.device)
+    assert masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() == b * nm * 4 * hh * ww
+    for t in (dbg_q3, x4):
+        assert t is None or (t.dtype == torch.int8 and t.is_contiguous() and t.numel() == b * 4 * hh * ww * cout)
+    _lib.check(_lib.load().samq_upscale1_masks_q8(_ptr(x), _ptr(w_hi), _ptr(w_lo), _ptr(bias), _ptr(hyper),
+                                                  _ptr(s_hyper), _ptr(masks), _ptr(dbg_q3), _ptr(x4), b, hh, ww, cin,
+                                                  cout, nm, float(s_in), float(s3), float(s4), float(s_q1), _stream()),
+               "upscale1_masks_q8")
+    return masks

@@ -5,15 +5,18 @@
 
 One click = ``prompt_encoder`` (one point) + ``mask_decoder`` on a fixed image embedding of a
 ``grid`` x ``grid`` map, timed on the host clock between device synchronisations, after warm-up.
-Three paths on the same calibrated model (default initialisation, minmax calibration on three random sets):
+Four paths on the same calibrated model (default initialisation, minmax calibration on three random sets):
 
-* ``graph``   the decoder engine replaying its captured HIP graph;
-* ``eager``   the decoder engine launching its kernels one by one;
+* ``graph_tail`` the decoder engine with the fused int8 tail, the whole click behind the prompt encoder
+  replayed from one captured HIP graph (``mask_decoder.use_fused_tail = True``, the default);
+* ``graph``   the engine's transformer replayed from its graph, then the module-graph tail
+  (``use_fused_tail = False``);
+* ``eager``   the same, the engine launching its kernels one by one;
 * ``modules`` the module graph of the same model on the GPU (``mask_decoder.use_engine = False``).
 
-Also counted: the kernel launches of one transformer forward on each path (torch profiler), and the
-launches of the module-graph tail (upscaling, hypernetwork MLPs, IoU head) that runs after the engine.
-One JSON line per path.
+Also counted (torch profiler): the launches of one click on each path, and in ``launch_split`` those of
+the prompt encoder, of one transformer forward, of the module-graph tail (upscaling, hypernetwork
+MLPs, IoU head) and of the fused tail.  One JSON line per path.
 """
 import argparse
 import json
@@ -100,11 +103,12 @@ def main():
         head = ""
     base = dict(grid=args.grid, clicks=args.clicks, device=torch.cuda.get_device_name(0), build=head,
                 torch=torch.__version__)
-    for path in ("graph", "eager", "modules"):
+    for path in ("graph_tail", "graph", "eager", "modules"):
         md.use_engine = path != "modules"
+        md.use_fused_tail = path == "graph_tail"
         eng.drop_graphs()
         click()
-        if path == "graph":
+        if path in ("graph", "graph_tail"):
             eng.capture(5 + 2)
         for _ in range(args.warmup):
             click()
@@ -118,14 +122,15 @@ def main():
         times.sort()
         rec = dict(base, path=path, ms_median=1e3 * times[len(times) // 2], ms_min=1e3 * times[0],
                    ms_p90=1e3 * times[int(0.9 * (len(times) - 1))])
-        if path != "graph":   # a replayed graph shows as one launch; its kernels are the eager engine's
-            rec["launches_per_click"] = launches(click)
+        # (a replayed graph's kernels are the eager engine's; the profiler lists them under the replay)
+        rec["launches_per_click"] = launches(click)
         line = json.dumps(rec)
         print(line, flush=True)
         if args.out:
             with open(args.out, "a") as f:
                 f.write(line + "\n")
-    md.use_engine = True
+    md.use_engine = md.use_fused_tail = True
+    eng.drop_graphs()
     # the parts of one eager click: prompt encoder, engine (transformer), module-graph tail
     with torch.no_grad():
         sparse, dense = pe(points=pts, boxes=None, masks=None)
@@ -136,6 +141,19 @@ def main():
                      prompt_encoder=launches(lambda: pe(points=pts, boxes=None, masks=None)),
                      engine=launches(lambda: eng.forward(emb, dense, dense_pe, tokens)),
                      tail=launches(lambda: md.heads_forward(hs, src, shape)))
+        qc = torch.zeros(tokens.shape, dtype=torch.int8, device=tokens.device)
+        kc = torch.zeros((args.grid * args.grid, emb.shape[1]), dtype=torch.int8, device=tokens.device)
+        parts["fused_tail"] = launches(lambda: eng._tail_run(qc, kc, 0.05, 0.05, eng._image, None))
+        parts["engine_masks"] = launches(lambda: eng.forward_masks(emb, dense, dense_pe, tokens))
+        # the prompt encoder's share of a click: its own wall time, same clock as the paths above
+        times = []
+        for i in range(args.warmup + args.clicks):
+            t0 = time.perf_counter()
+            pe(points=pts, boxes=None, masks=None)
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                times.append(time.perf_counter() - t0)
+        parts["prompt_encoder_ms_median"] = 1e3 * sorted(times)[len(times) // 2]
     print(json.dumps(dict(base, **parts)), flush=True)
     if args.out:
         with open(args.out, "a") as f:
