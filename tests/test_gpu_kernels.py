@@ -382,7 +382,7 @@ def test_rel_attention(cuda, b, h, w, heads, d, window):
 
 @pytest.mark.parametrize("b,h,w,heads,d,window", [
     (2, 64, 64, 16, 80, 14),    # ViT-H windowed lane (two-workgroups-per-CU window kernel)
-    (2, 64, 64, 16, 80, 0),     # ViT-H global lane (streaming kernel)
+    (2, 64, 64, 16, 80, 0),     # ViT-H global lane (32x32-MFMA kernel)
     (1, 20, 33, 3, 64, 14),     # ragged grid, vit_b head dim
     (3, 16, 16, 2, 80, 0),      # resident small global grid
     (2, 32, 32, 8, 64, 0),      # streaming kernel, XCD-remapped 1-D grid
