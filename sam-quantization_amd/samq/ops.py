@@ -289,7 +289,10 @@ def rel_attention(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], rel_pos_h
     if out is None:
         out = torch.empty((b, h, w, c), dtype=odt, device=qkv.device)
     assert out.dtype == odt and out.is_contiguous()
-    args = (_ptr(qkv), _ptr(qkv_bias), _ptr(rel_pos_h.contiguous()), _ptr(rel_pos_w.contiguous()), _ptr(out),
+    # named, so a copy made here lives until the launch is queued (a temporary's block would be handed
+    # to the next copy, and the kernel would read that one's data)
+    rel_pos_h, rel_pos_w = rel_pos_h.contiguous(), rel_pos_w.contiguous()
+    args = (_ptr(qkv), _ptr(qkv_bias), _ptr(rel_pos_h), _ptr(rel_pos_w), _ptr(out),
             b, h, w, heads, hd, window, float(sm_scale))
     if out_scale > 0:
         _lib.check(_lib.load().samq_rel_attention_q(*args, float(out_scale), _stream()), "rel_attention_q")
@@ -305,8 +308,10 @@ def attention_relbias(inp: torch.Tensor, rel_h: torch.Tensor, rel_w: torch.Tenso
     b, h, w, c3 = inp.shape
     assert h == w, "the reference kernel requires square grids (emb_len = rel.shape[-1])"
     out = torch.empty((b, h, w, c3 // 3), dtype=inp.dtype, device=inp.device)
-    _lib.check(_lib.load().samq_attention_relbias(_ptr(inp.contiguous()), _ptr(rel_h.half().contiguous()),
-                                                  _ptr(rel_w.half().contiguous()), _ptr(out), b, h, heads, hd,
+    # named, so the fp16 / contiguous copies live until the launch is queued: the block of a temporary
+    # rel_h copy would be handed to the rel_w copy, and the kernel would read rel_w for both
+    inp, rel_h, rel_w = inp.contiguous(), rel_h.half().contiguous(), rel_w.half().contiguous()
+    _lib.check(_lib.load().samq_attention_relbias(_ptr(inp), _ptr(rel_h), _ptr(rel_w), _ptr(out), b, h, heads, hd,
                                                   float(sm_scale), _stream()), "attention_relbias")
     return out
 
@@ -608,8 +613,9 @@ def rel_attention_q8(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], rel_po
     if out is None:
         out = torch.empty((b, h, w, c), dtype=torch.int8, device=qkv.device)
     r0, nr = rows if rows is not None else (0, -1)
+    rel_pos_h, rel_pos_w = rel_pos_h.contiguous(), rel_pos_w.contiguous()   # named: see rel_attention
     _lib.check(_lib.load().samq_rel_attention_q8_rows(
-        _ptr(qkv), _ptr(qkv_bias), _ptr(rel_pos_h.contiguous()), _ptr(rel_pos_w.contiguous()), _ptr(out), b, h, w,
+        _ptr(qkv), _ptr(qkv_bias), _ptr(rel_pos_h), _ptr(rel_pos_w), _ptr(out), b, h, w,
         heads, c // heads, window, float(sm_scale), float(s_qkv), float(s_a1), float(s_a2), float(s_out), int(r0),
         int(nr), _ptr(v16), _stream()), "rel_attention_q8")
     return out

@@ -72,12 +72,44 @@ def q8_inputs(b, h, w, heads, window, seed, d):
 
 EXACT_SM_SCALE = 2.0 ** -3
 
+# Sharp-softmax variants of the "saturating" codes: the kernels move their exp2 offset only when a
+# score code exceeds it by more than lazyc = min(floor(8 / (s_a2 log2e)), 255) codes and index the
+# P table by c - m.  At s_a2 = 2^-6 lazyc is capped at 255 (the offset never moves after its first
+# value) and at 2^-4 it is 88; a real checkpoint calibrates s_a2 to a few tenths.
+#   "peaked": s_a2 = 2^-1, lazyc = 11;   "needle": s_a2 = 2^1, lazyc = 2 (near one-hot rows).
+# s_out is not a power of two: with one-hot rows a power-of-two s_out puts o / s_out on exact ties
+# that the fp32 and fp64 references resolve differently.
+PEAKED_VARIANTS = ("peaked", "needle")
+PEAKED_S_A2 = {"peaked": 2.0 ** -1, "needle": 2.0 ** 1}
+PEAKED_LAZYC = {"peaked": 11, "needle": 2}
+PEAKED_S_OUT = np.float32(0.0371)
+
+
+def lazy_codes(s_a2):
+    """lazyc of csrc/attention_q8.hip (q8_ptab_lazy), in the kernel's fp32 arithmetic."""
+    k2 = np.float32(s_a2) * np.float32(1.4426950408889634)
+    return int(min(np.floor(np.float32(8.0) / k2), 255))
+
+
+def offset_moves_after_row0(codes2, side, lazyc):
+    """Replay of the lazy offset over the key rows of the second quantiser's codes ((n, L, L) int16
+    tensors, L = side^2): how often m moves (a row max above m + lazyc) after the first key row."""
+    moves = 0
+    for t in codes2:
+        rowmax = t.view(t.shape[0], t.shape[1], side, side).amax(-1).to(torch.int32)   # (n, L, key row)
+        m = rowmax[..., 0].clone()
+        for r in range(1, side):
+            up = rowmax[..., r] > m + lazyc
+            m = torch.where(up, rowmax[..., r], m)
+            moves += int(up.sum())
+    return moves
+
 
 def exact_attn_inputs(b, h, w, heads, window, variant, seed, d):
     """``test_w8a8._exact_attn_inputs`` at head dim d, to be used with sm_scale = 2^-3 and
     s_qkv = 2^-5: q.k * scale = int * 2^-13 with |int| <= d * 2^14 (< 2^21 at d = 80), rel_h, rel_w =
     int * 2^-9 with |int| <= d * 2^10 (< 2^17) -- every score-side value is exact in fp32 in any
-    summation order.  Variants "fine" and "saturating" as there.
+    summation order.  Variants "fine", "saturating", "peaked" and "needle" as there.
     Returns (qkv, bias, relh, relw, (s_qkv, s_a1, s_a2, s_out))."""
     c = heads * d
     side = window or h
@@ -94,12 +126,14 @@ def exact_attn_inputs(b, h, w, heads, window, variant, seed, d):
         qkv[..., :2 * c] = rng.integers(-16, 16, (b, h, w, 2 * c), dtype=np.int8)
         scales = (s_qkv, np.float32(2.0 ** -9), np.float32(2.0 ** -6), np.float32(2.0 ** -3 / side))
     else:
-        assert variant == "saturating"
+        assert variant in ("saturating",) + PEAKED_VARIANTS
         qkv = rng.integers(-128, 128, (b, h, w, 3 * c), dtype=np.int8)
         tok = qkv.reshape(b, h * w, 3 * c)
         tok[:, 0:3, :2 * c] = 127
         tok[:, 3:5, :2 * c] = -128
         scales = (s_qkv, np.float32(2.0 ** -6), np.float32(2.0 ** -4), np.float32(2.0 ** -6))
+        if variant in PEAKED_VARIANTS:
+            scales = (s_qkv, scales[1], np.float32(PEAKED_S_A2[variant]), PEAKED_S_OUT)
     return qkv, bias, relh, relw, scales
 
 

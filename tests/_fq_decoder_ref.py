@@ -196,13 +196,23 @@ def attn_inputs(case, seed=0):
 EXACT_CASES = [(1, 8, 16, 7, 192), (1, 8, 16, 100, 9), (1, 8, 32, 6, 6)]
 
 
-def exact_attn_inputs(case, seed=0):
+# "peaked" scale set: s_q = s_k = 1, s_a1 = 2^-1 -- q.k s_q s_k / sqrt(D) / s_a1 is dot / 2 as with the
+# plain set (the same integer score codes, the same exact ties), the softmax argument code * s_a1
+# 16 times larger: one code step is a factor e^0.5, rows are near one-hot, and the running maxima of
+# the lanes, waves and workgroup partial states lie many e-folds apart.  With the two larger cases:
+# keys over the lanes at 8 waves (Nk = 4096) and one lane per query past one block (Nq = 300).
+EXACT_PEAKED_CASES = EXACT_CASES + [(1, 8, 16, 9, 4096), (1, 8, 16, 300, 70)]
+EXACT_PEAKED_SCORE_SCALES = (1.0, 1.0, 2.0 ** -1)     # s_q, s_k, s_a1
+
+
+def exact_attn_inputs(case, seed=0, peaked=False):
     """Small integer codes and power-of-two scales: q.k * s_q s_k / sqrt(D) / s_a1 = dot / 2 at
     D = 16 (every odd dot an exact tie of the score quantiser, D = 32: dot / (2 sqrt 2)), scores a
     few codes apart so many keys carry weight; v codes * 2^-3.  s_out is NOT a power of two: after the
     softmax no output quotient is exact, and a power-of-two s_out would put the uniform rows' (query 0,
     all zero) quotients sum(v) / (Nk / 2) on exact .5 ties that neither fp32 nor fp64 resolves the
     same way -- the condition test_exact_attention_inputs_fp32_vs_fp64 checks.
+    ``peaked``: the same codes with EXACT_PEAKED_SCORE_SCALES.
     Returns (q, k, v, scales)."""
     b, h, d, nq, nk = case
     rng = np.random.Generator(np.random.PCG64(4321 + seed + zlib.crc32(repr(case).encode())))
@@ -210,7 +220,8 @@ def exact_attn_inputs(case, seed=0):
     k = rng.integers(-3, 4, (b, nk, h * d), dtype=np.int8)
     v = rng.integers(-128, 128, (b, nk, h * d), dtype=np.int8)
     q[:, 0, :] = 0
-    return q, k, v, (2.0 ** -2, 2.0 ** -2, 2.0 ** -3, 2.0 ** -5, float(np.float32(0.0371)))
+    s_q, s_k, s_a1 = EXACT_PEAKED_SCORE_SCALES if peaked else (2.0 ** -2, 2.0 ** -2, 2.0 ** -5)
+    return q, k, v, (s_q, s_k, 2.0 ** -3, s_a1, float(np.float32(0.0371)))
 
 
 # (B, H, D, Nq, Nk): uniform softmax rows whose output quotients are exact, ties included -- one lane per

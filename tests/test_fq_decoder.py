@@ -186,6 +186,21 @@ def test_exact_attention_inputs_fp32_vs_fp64(case):
     assert mx <= 1 and frac <= 1e-4
 
 
+@pytest.mark.parametrize("case", R.EXACT_PEAKED_CASES, ids=str)
+def test_exact_peaked_attention_inputs_fp32_vs_fp64(case):
+    """The same condition at the sharp softmax scale (s_a1 = 2^-1): the codes are those of the plain
+    set and so are the integer score codes."""
+    q, k, v, scales = R.exact_attn_inputs(case, peaked=True)
+    plain = R.exact_attn_inputs(case)
+    assert all(np.array_equal(x, y) for x, y in zip((q, k, v), plain[:3]))
+    assert scales[0] * scales[1] / scales[3] == plain[3][0] * plain[3][1] / plain[3][3]   # the same score codes
+    a = R.attention_ref(q, k, v, case[1], *scales, dtype=torch.float32)
+    b = R.attention_ref(q, k, v, case[1], *scales, dtype=torch.float64)
+    mx, frac = R.off_by_one(a, b)
+    print(f"[exact peaked inputs] {case}: fp32 vs fp64 max {mx:.0f}, {frac:.2e} off by one")
+    assert mx <= 1 and frac <= 1e-4
+
+
 def test_decoder_kernels_refuse_unsupported_shapes():
     """The documented error codes, before anything reaches the device (runs without a GPU)."""
     from samq import _lib
@@ -248,6 +263,19 @@ def test_attention_q8_plain_exact_ties(cuda, case):
     out = _attn_gpu(cuda, q, k, v, case[1], scales)
     _codes_close(out, ref, 1e-4, f"exact attention {case}")
     # query 0 (all-zero codes): equal scores on every key, in every key chunk -> the mean of v
+    mean_v = v.astype(np.float64).mean(axis=1) * scales[2] / scales[4]
+    assert np.abs(out[:, 0].astype(np.float64) - np.clip(mean_v, -128, 127)).max() <= 0.5 + 1e-3
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", R.EXACT_PEAKED_CASES, ids=str)
+def test_attention_q8_plain_exact_ties_peaked(cuda, case):
+    """test_attention_q8_plain_exact_ties at the sharp softmax scale (s_a1 = 2^-1): near one-hot rows,
+    partial softmax states of lanes and waves whose integer maxima lie far apart."""
+    q, k, v, scales = R.exact_attn_inputs(case, peaked=True)
+    ref = R.attention_ref(q, k, v, case[1], *scales, dtype=torch.float64)
+    out = _attn_gpu(cuda, q, k, v, case[1], scales)
+    _codes_close(out, ref, 1e-4, f"exact peaked attention {case}")
     mean_v = v.astype(np.float64).mean(axis=1) * scales[2] / scales[4]
     assert np.abs(out[:, 0].astype(np.float64) - np.clip(mean_v, -128, 127)).max() <= 0.5 + 1e-3
 

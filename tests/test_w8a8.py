@@ -16,6 +16,10 @@ import pytest
 import torch
 
 from oracle import fq_ref, sam_ref, synth
+# "peaked" / "needle": the saturating codes at s_a2 = 2^-1 / 2^1 (lazyc = 11 / 2), see _attn_q8_ref
+from _attn_q8_ref import (PEAKED_LAZYC as _PEAKED_LAZYC, PEAKED_S_A2 as _PEAKED_S_A2, PEAKED_S_OUT as _PEAKED_S_OUT,
+                          PEAKED_VARIANTS as _PEAKED_VARIANTS, lazy_codes as _lazy_codes,
+                          offset_moves_after_row0 as _offset_moves_after_row0)
 
 
 def _golden_model(golden_dir, tag, img_size):
@@ -546,12 +550,14 @@ def _exact_attn_inputs(b, h, w, heads, window, variant, seed):
         qkv[..., :2 * c] = rng.integers(-16, 16, (b, h, w, 2 * c), dtype=np.int8)
         scales = (s_qkv, np.float32(2.0 ** -9), np.float32(2.0 ** -6), np.float32(2.0 ** -3 / side))
     else:
-        assert variant == "saturating"
+        assert variant in ("saturating",) + _PEAKED_VARIANTS
         qkv = rng.integers(-128, 128, (b, h, w, 3 * c), dtype=np.int8)
         tok = qkv.reshape(b, h * w, 3 * c)
         tok[:, 0:3, :2 * c] = 127
         tok[:, 3:5, :2 * c] = -128
         scales = (s_qkv, np.float32(2.0 ** -6), np.float32(2.0 ** -4), np.float32(2.0 ** -6))
+        if variant in _PEAKED_VARIANTS:
+            scales = (s_qkv, scales[1], np.float32(_PEAKED_S_A2[variant]), _PEAKED_S_OUT)
     return qkv, bias, relh, relw, scales
 
 
@@ -566,7 +572,7 @@ def _fq_low127(x, s):
     return torch.clamp(torch.round(x / s), -127, 127) * s
 
 
-@pytest.mark.parametrize("variant", ["fine", "saturating"])
+@pytest.mark.parametrize("variant", ["fine", "saturating", "peaked", "needle"])
 @pytest.mark.parametrize("b,hw,window", [(1, 20, 14), (1, 16, 0)])
 def test_exact_attn_inputs_pin_the_quantisers(b, hw, window, variant):
     """CPU: what test_rel_attention_q8_exact_ties relies on.  On _exact_attn_inputs the float32 and
@@ -581,7 +587,11 @@ def test_exact_attn_inputs_pin_the_quantisers(b, hw, window, variant):
     deviation of ~340 codes, so ~70 % of the first quantiser's arguments lie beyond the clamp and
     only 1/128 of the rest are ties; one of those moves the second quantiser's argument by a
     quarter of a code.  Measured over seeds 0-3: 9e-5 to 8e-4 of the output codes.  The "fine"
-    variant is the one that pins that rounding mode (> 6e-3 on both geometries)."""
+    variant is the one that pins that rounding mode (> 6e-3 on both geometries).
+
+    "peaked" / "needle" (the saturating codes at s_a2 = 2^-1 / 2^1) are there for the softmax, not for
+    the quantisers: the same fp32-vs-fp64 condition holds, the wrong-quantiser shares are printed
+    only, and the lazy offset must move after the first key row (lazyc = 11 / 2)."""
     heads = 2
     qkv, bias, relh, relw, scales = _exact_attn_inputs(b, hw, hw, heads, window, variant, seed=hw + window)
     c32, c64 = [], []
@@ -594,7 +604,14 @@ def test_exact_attn_inputs_pin_the_quantisers(b, hw, window, variant):
     print(f"\n[exact {variant} {b}x{hw} win {window}] second-quantiser codes at 127: {hi:.3f}, at -128: {lo:.3f}; "
           f"output codes fp32 vs fp64 {own:.2e}")
     assert np.abs(ref32 - ref64).max() <= 1 and own <= 1e-4
-    assert hi > 0 and lo > 0    # both clamp ends are exercised
+    if variant not in _PEAKED_VARIANTS:
+        assert hi > 0 and lo > 0    # both clamp ends are exercised
+    else:   # codes span about +-95 / +-24: the first quantiser saturates, the second does not
+        lazyc = _lazy_codes(scales[2])
+        moves = _offset_moves_after_row0(c64, window or hw, lazyc)
+        print(f"    lazyc {lazyc}, second-quantiser codes {int(codes.min())}..{int(codes.max())}, "
+              f"offset moves after the first key row: {moves}")
+        assert lazyc == _PEAKED_LAZYC[variant] and moves > 0
     for what, kw in [("half-away at quantiser 1", dict(fq1=_fq_half_away)),
                      ("half-away at quantiser 2", dict(fq2=_fq_half_away)),
                      ("low clamp -127", dict(fq1=_fq_low127, fq2=_fq_low127))]:
@@ -602,7 +619,8 @@ def test_exact_attn_inputs_pin_the_quantisers(b, hw, window, variant):
         frac = float((wrong != ref64).mean())
         print(f"    {what}: {frac:.2e} of the output codes change")
         weak = variant == "saturating" and what == "half-away at quantiser 1"   # see the docstring
-        assert frac > (1e-4 if weak else 10 * 1e-4), what
+        if variant not in _PEAKED_VARIANTS:
+            assert frac > (1e-4 if weak else 10 * 1e-4), what
 
 
 _EXACT_GEOMETRIES = {
@@ -616,7 +634,7 @@ _EXACT_GEOMETRIES = {
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["fine", "saturating"])
+@pytest.mark.parametrize("variant", ["fine", "saturating", "peaked", "needle"])
 @pytest.mark.parametrize("geom", list(_EXACT_GEOMETRIES))
 def test_rel_attention_q8_exact_ties(cuda, geom, variant):
     """Rounding mode and clamp ends of the two score quantisers (and of the pad-token codes), per
@@ -627,7 +645,8 @@ def test_rel_attention_q8_exact_ties(cuda, geom, variant):
     (test_exact_attn_inputs_pin_the_quantisers).
     Measured on gfx950 (share of differing codes, all within +-1): largest 2.29e-5 (glob64 fine, the
     same with int8 and fp16 V); glob32 7.6e-6 / 1.5e-5 (fine / saturating), glob64 saturating 1.9e-6,
-    win14 fine 5.9e-6, every other case 0."""
+    win14 fine 5.9e-6, every other case 0.  "peaked" / "needle" (lazyc = 11 / 2, the offset moves on
+    most key rows): peaked 0 except glob64 2.67e-5; needle 0 to 2.48e-5 (glob64), int8 and fp16 V alike."""
     b, h, w, heads, window = _EXACT_GEOMETRIES[geom]
     qkv, bias, relh, relw, scales = _exact_attn_inputs(b, h, w, heads, window, variant, seed=h + w + window)
     ref = _attn_ref(qkv, bias, relh, relw, heads, window, *scales, dtype=torch.float64)
