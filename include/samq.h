@@ -169,7 +169,9 @@ int samq_w4a8_gemm(const int8_t* A, int64_t lda, const int32_t* wpacked, const f
                    int K, int groupsize, int epilogue, float a_scale, float out_scale,
                    hipStream_t stream);
 /* The same with an explicit tile config (0 = automatic; per-channel: as samq_i8_gemm_cfg; grouped:
- * 83 128x128, 84 64x64, 87 128x64, 88 64x128). */
+ * 83 128x128, 84 64x64, 87 128x64, 88 64x128, the other ids of samq_i8_gemm_cfg return
+ * SAMQ_ERR_INVALID for grouped weights).  Any id samq_i8_gemm_cfg does not list returns
+ * SAMQ_ERR_INVALID with "unknown tile config". */
 int samq_w4a8_gemm_cfg(const int8_t* A, int64_t lda, const int32_t* wpacked, const float* wscale,
                        const int32_t* qzeros, const float* bias, void* C, int64_t ldc, int M, int N,
                        int K, int groupsize, int epilogue, float a_scale, float out_scale, int cfg,
@@ -177,15 +179,16 @@ int samq_w4a8_gemm_cfg(const int8_t* A, int64_t lda, const int32_t* wpacked, con
 
 /* samq_w8a8_gemm with the Q8 epilogue (the fq_vit qkv QLinear + attn.qact1) that also stores the
  * codes of output columns [v_col0, N) as fp16 values into v16 [M, ldv] (column c at c - v_col0): the V
- * third of qkv for samq_rel_attention_q8_rows' v16 (round 6).  v_col0 % 64 == 0. */
+ * third of qkv for samq_rel_attention_q8_rows' v16.  v_col0 % 64 == 0.  cfg: 0 = automatic or a
+ * tile config of samq_i8_gemm_cfg that takes W8 weights. */
 int samq_w8a8_gemm_v16(const int8_t* A, int64_t lda, const int8_t* wpacked, const float* wscale,
                        const float* bias, int8_t* C, int64_t ldc, int M, int N, int K, float a_scale,
                        float out_scale, void* v16, int v_col0, int64_t ldv, int cfg, hipStream_t stream);
 
-/* Per-channel W4A8 GEMM with the zero point's row sums moved to the producers (round 6):
- * rowsum_in (optional, int32 [M]) = S[m] = sum_k A[m, k] of the int8 input rows -- the zero-point
- * ping-pong (cfg 86 / 93) then subtracts zp[n] * S[m] without re-summing A per column tile; kernels
- * without the row-sum form ignore it.  rowsum_out (optional, int32 [M], ZEROED by the caller;
+/* Per-channel W4A8 GEMM with the zero point's row sums moved to the producers:
+ * rowsum_in (optional, int32 [M]) = S[m] = sum_k A[m, k] of the int8 input rows -- the ping-pong
+ * kernel (cfg 86) then subtracts zp[n] * S[m] without re-summing A per column tile; the other tile
+ * configs ignore it.  cfg as for samq_i8_gemm_cfg with W4 weights.  rowsum_out (optional, int32 [M], ZEROED by the caller;
  * epilogue Q8 / Q8_GELU only) accumulates the row sums of the int8 output codes with atomics, the
  * next GEMM's rowsum_in (replaces the per-tile row sums of quant_linear.py:299-343's zero-point
  * subtraction; fq_vit uniform.py:23-45 codes).  Outputs are bit-identical to samq_w4a8_gemm_cfg. */
@@ -195,7 +198,17 @@ int samq_w4a8_gemm_rs(const int8_t* A, int64_t lda, const int32_t* wpacked, cons
                       int32_t* rowsum_out, int cfg, hipStream_t stream);
 
 /* Both int8 GEMMs with an explicit weight format (0 = W8 packed, 1 = W4 layout 3) and tile
- * config (0 = automatic; 81 256x256, 82 128x256, 83 128x128, 84 64x64); for tuning and tests. */
+ * config; for tuning and tests.  cfg (N must be a multiple of the tile width, else
+ * SAMQ_ERR_INVALID):
+ *     0  automatic
+ *     3-slot LDS ring (W4: 3 slots, W8: 2 for 81): 81 256x256, 82 128x256, 83 128x128, 84 64x64,
+ *          87 128x64, 88 64x128
+ *     2-slot ring: 89 64x64, 90 64x128, 91 32x64, 92 64x32, 180 128x128, 181 128x64,
+ *          182 128x128 on 8 waves
+ *     85 / 86  W4 only (SAMQ_ERR_INVALID for W8): the 256x256 ping-pong kernel; 86 with the zero
+ *          point through the row sums of A (K < 65536, else SAMQ_ERR_UNSUPPORTED)
+ * Any other id (the tuning build's timing-only configs among them) returns SAMQ_ERR_INVALID
+ * with "unknown tile config". */
 int samq_i8_gemm_cfg(const int8_t* A, int64_t lda, int bfmt, const void* wpacked, const float* wscale,
                      const int32_t* qzeros, const float* bias, void* C, int64_t ldc, const int8_t* R,
                      int64_t ldr, int M, int N, int K, int epilogue, float a_scale, float mid_scale,

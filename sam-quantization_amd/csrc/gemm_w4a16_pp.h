@@ -210,7 +210,7 @@ __device__ __forceinline__ void pp_epilogue(const float16_t (&acc)[TM][TN], cons
                                                  (float2_t)(lnf_consumer(EPI) ? 0.0f : cb[t]));
           if (EPI == SAMQ_EPI_BIAS_GELU) v = gelu_fast2(v);
           // f16 outputs: the 4-column chunk XOR ((rl >> 1) & 1) within each 8 columns, so the two
-          // 16-byte reads of a lane group's 4 rows land on distinct banks (gemm_i8.hip i8_epilogue)
+          // 16-byte reads of a lane group's 4 rows land on distinct banks (gemm_i8_epilogue.h)
           const int cs = (t * 32 + (lane & 31)) ^ (F16SWZ ? 4 * ((rl >> 1) & 1) : 0);
           ep[rl * WN + cs] = v.x;
           ep[(rl + 1) * WN + cs] = v.y;

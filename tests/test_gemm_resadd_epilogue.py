@@ -37,9 +37,9 @@ MS = (1, 255, 277)
 # 108 the persistent forms and 110 the early scale / bias loads
 W4A16_CFGS = (0, 1, 5, 22, 29, 57, 62, 64, 107, 108, 110)
 W4A16_GROUPED = ((57, 192, 64), (64, 192, 64), (22, 192, 64))          # (cfg, K, groupsize)
-# W4A8: 85 / 86 / 93 the ping-pong kernel (86 / 93 with and without the producer's row sums), 0 the
-# automatic pick and 81 / 82 the 3-slot kernel with 256- and 128-row tiles; grouped: 0 and 83
-W4A8_CFGS = (0, 81, 82, 85, 86, 93)
+# W4A8: 85 / 86 the ping-pong kernel (86 with and without the producer's row sums), 0 the automatic
+# pick and 81 / 82 the 3-slot kernel with 256- and 128-row tiles; grouped: 0 and 83
+W4A8_CFGS = (0, 81, 82, 85, 86)
 W4A8_GROUPED = ((0, 384, 128), (83, 384, 128))
 
 
@@ -169,11 +169,11 @@ def _w4a8_case(cuda, cfg, k, group, m, n, with_rowsum):
 @pytest.mark.parametrize("m", MS)
 @pytest.mark.parametrize("cfg", W4A8_CFGS)
 def test_w4a8_resadd_batched(cuda, cfg, m, k):
-    """The W4A8 GEMM, per channel: the ping-pong kernel forced (85, 86, 93; 86 and 93 also with the
-    producer's row sums of A), the automatic pick and the 3-slot kernel (81, 82); K = 128 and 384
-    (one and three 128-deep K tiles).  The same checks as for W4A16."""
+    """The W4A8 GEMM, per channel: the ping-pong kernel forced (85, 86; 86 also with the producer's
+    row sums of A), the automatic pick and the 3-slot kernel (81, 82); K = 128 and 384 (one and three
+    128-deep K tiles).  The same checks as for W4A16."""
     for n in (256, 512):
-        for with_rowsum in ((False, True) if cfg in (86, 93) else (False,)):
+        for with_rowsum in ((False, True) if cfg == 86 else (False,)):
             _w4a8_case(cuda, cfg, k, 0, m, n, with_rowsum)
 
 

@@ -97,6 +97,65 @@ def test_c_abi_rejects_timing_and_layout2_configs():
     assert q.gemm_cfg == 22
 
 
+def test_c_abi_int8_gemm_config_table():
+    """The int8 GEMM tile-config table of the product library holds exactly ops.I8_CFGS.  Through
+    every entry point that takes a config (samq_i8_gemm_cfg on both weight formats, samq_w4a8_gemm_cfg
+    with grouped weights, samq_w8a8_gemm_v16, samq_w4a8_gemm_rs) every other id in 1..255 -- the ids
+    of removed kernels (93, 95, 98, 99) and the tuning build's timing-only 94, 96, 97 among them
+    -- answers SAMQ_ERR_INVALID with "unknown tile config", whatever N is.  A known id answers "N not
+    divisible by tile" for N = BN + 64 (the entry points need N % 64 == 0, so only ids with BN > 64
+    have such an N).  Configs 85 / 86 refuse W8 weights and the grouped path refuses every id but 83 / 84
+    / 87 / 88.  All of it before any device work (no launch happens: the pointers are not device
+    memory)."""
+    from samq import _lib, ops
+    import test_i8_gemm as G
+    lib = _lib.load()
+    p = ctypes.c_void_p(4096)
+    k = 256
+
+    def i8(bfmt, cfg, n):
+        st = lib.samq_i8_gemm_cfg(p, k, bfmt, p, p, p, None, p, 4096, None, 0, 77, n, k, _lib.EPI_F32, 1.0, 0.0, 0.0,
+                                  0.0, cfg, None)
+        return st, lib.samq_last_error().decode()
+
+    def grouped(cfg, n):
+        st = lib.samq_w4a8_gemm_cfg(p, k, p, p, p, None, p, 4096, 77, n, k, 128, _lib.EPI_F32, 1.0, 0.0, cfg, None)
+        return st, lib.samq_last_error().decode()
+
+    def v16(cfg, n):
+        st = lib.samq_w8a8_gemm_v16(p, k, p, p, None, p, 4096, 77, n, k, 1.0, 0.05, p, 0, 4096, cfg, None)
+        return st, lib.samq_last_error().decode()
+
+    def rs(cfg, n):
+        st = lib.samq_w4a8_gemm_rs(p, k, p, p, p, None, p, 4096, 77, n, k, _lib.EPI_F32, 1.0, 0.0, None, None, cfg, None)
+        return st, lib.samq_last_error().decode()
+
+    calls = [lambda c, n: i8(_lib.BF_W8, c, n), lambda c, n: i8(_lib.BF_W4, c, n), grouped, v16, rs]
+    assert {93, 94, 95, 96, 97, 98, 99}.isdisjoint(ops.I8_CFGS)
+    for cfg in range(1, 256):
+        if cfg in ops.I8_CFGS:
+            continue
+        for call in calls:
+            for n in (768, 320):   # 320: no multiple of a 256- or 128-column tile either
+                st, msg = call(cfg, n)
+                assert st == _lib.SAMQ_ERR_INVALID and "unknown tile config" in msg, (cfg, n, st, msg)
+    assert set(G.TILES) == set(ops.I8_CFGS)
+    for cfg, (_, bn) in G.TILES.items():
+        for call in calls:
+            if bn > 64:
+                n = bn + 64 if (bn + 64) % bn else 2 * bn + 64
+                st, msg = call(cfg, n)
+                assert st == _lib.SAMQ_ERR_INVALID and "N not divisible by tile" in msg, (cfg, n, st, msg)
+            st, msg = call(cfg, 96)
+            assert st == _lib.SAMQ_ERR_INVALID and "64" in msg, (cfg, st, msg)
+    for cfg in (85, 86):
+        for st, msg in (i8(_lib.BF_W8, cfg, 768), v16(cfg, 768)):
+            assert st == _lib.SAMQ_ERR_INVALID and f"cfg {cfg} is the W4 ping-pong kernel" in msg, (cfg, st, msg)
+    for cfg in sorted(ops.I8_CFGS - {83, 84, 87, 88}):
+        st, msg = grouped(cfg, 768)
+        assert st == _lib.SAMQ_ERR_INVALID and "grouped weights take tile configs 83 / 84 / 87 / 88" in msg, (cfg, st, msg)
+
+
 @pytest.mark.parametrize("tag,g", [("gm1", -1), ("g128", 128)])
 def test_product_packer_bit_exact_vs_reference(golden_dir, tag, g):
     from samq.gptq import pack_linear, rtn

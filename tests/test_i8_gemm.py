@@ -14,12 +14,12 @@ import torch
 
 import _i8_ref as R
 
-# BM, BN of launch_i8_cfg (csrc/gemm_i8.hip)
+# BM, BN of with_i8_cfg (csrc/gemm_i8.hip)
 TILES = {81: (256, 256), 82: (128, 256), 83: (128, 128), 84: (64, 64), 85: (256, 256), 86: (256, 256),
-         87: (128, 64), 88: (64, 128), 89: (64, 64), 90: (64, 128), 91: (32, 64), 92: (64, 32), 93: (256, 256),
+         87: (128, 64), 88: (64, 128), 89: (64, 64), 90: (64, 128), 91: (32, 64), 92: (64, 32),
          180: (128, 128), 181: (128, 64), 182: (128, 128)}
 W8_CFGS = [0, 81, 82, 83, 84, 87, 88, 89, 90, 91, 92, 180, 181, 182]
-W4_CFGS = W8_CFGS + [85, 86, 93]
+W4_CFGS = W8_CFGS + [85, 86]
 GROUPED_CFGS = [0, 83, 84, 87, 88]
 GROUPED_KG = [(384, 128), (640, 256), (640, 128)]      # (640, 256): a ragged last group
 # cfg 0: shapes on which i8_pick_cfg (M <= 1024) takes each config it can reach -- W8: 89 (any N),
@@ -126,10 +126,10 @@ class _Case:
         self.dv = _dev(p, n, dev)
         self.a = _a_window(p, m, dev)
         self.tag = f"{p.fmt} cfg {cfg} {m}x{n}x{p.k}" + (f" g{p.group}" if p.group else "")
-        self.rowsum_in = _t(p.rowsum_a[:m], dev) if (p.fmt == "w4" and cfg in (86, 93)) else None
+        self.rowsum_in = _t(p.rowsum_a[:m], dev) if (p.fmt == "w4" and cfg == 86) else None
 
     def _rs_variants(self):
-        """Per launch: no row sums; on cfg 86 / 93 also with the producer's exact sums of A."""
+        """Per launch: no row sums; on cfg 86 also with the producer's exact sums of A."""
         return [{}] + ([dict(rowsum=self.rowsum_in)] if self.rowsum_in is not None else [])
 
     def run(self, epi, dtype, sentinel, prefill=None, res=None, extra=3, **kw):
@@ -240,18 +240,19 @@ def test_exact_i8_inputs_pin_the_epilogues(fmt, k, group):
 @pytest.mark.gpu
 @pytest.mark.parametrize("fmt,cfg,k,group", CASES, ids=_CASE_IDS)
 def test_i8_gemm_tile_configs(cuda, fmt, cfg, k, group):
-    """Every tile config of launch_i8_cfg / launch_i8_grouped on both weight formats, K = 128 (one K
+    """Every tile config of with_i8_cfg (per channel and grouped) on both weight formats, K = 128 (one K
     tile, shorter than any ring), 256, 384 and 640 (five tiles: wraps the 2- and the 3-slot ring),
     every epilogue but BIAS_GELU (below), at shapes A and B of _shapes().  F32, RESADD_F32, BIAS (= float16(y)), Q8 and
     Q8_RES (in place; separate R with ldr != ldc; mid_scale = 0) equal the float64 reference
     exactly, in the "fine" and the saturating variant.  W4 per channel: rowsum_out = prefill + the
-    row sums of the written codes on every config; cfg 86 / 93 give the same bits with the producer's
+    row sums of the written codes on every config; cfg 86 gives the same bits with the producer's
     row sums of A.
 
     Q8_GELU goes through the approximate GELU (gelu_r16_2, documented |error| 7.1e-7, fp32
     emulation): a code may differ from the float64 erf reference by one step, and only where the
     reference quotient lies within E / out_scale + 2 fp32 ulps of the midpoint, E = 1.42e-6
-    (_i8_ref.check_gelu_q8).  Measured on gfx950 over all 139 cases, every difference one step: "fine"
+    (_i8_ref.check_gelu_q8).  Measured on gfx950 over 139 cases (these and a since-removed W4
+    config), every difference one step: "fine"
     (out_scale 3 * 2^-7 / 2^-8) at most 5.5e-5 of a case's codes differ, the farthest 2.6e-5 of a
     code = 3.0e-7 from its midpoint; saturating (3 * 2^-13 / 2^-14) at most 3.4e-4 differ, the
     farthest 2.4e-3 of a code = 4.3e-7 from its midpoint (0.3 E).  The fp16 GELU epilogue is
@@ -296,7 +297,8 @@ def test_i8_gemm_bias_gelu_f16(cuda, fmt, cfg, k, group):
     of the boundary), but 1.0e-2 .. 2.4e-2 of the outputs were 2 .. 8 fp16 steps off, all of them
     with |GELU(y)| <= 4.9e-4 (y in [-5.03, -3.64]) where one fp16 step is 6.0e-8 .. 2.4e-7, finer
     than an absolute error of 5e-7.  The epilogue now takes gelu_erfc2 (library erfc: relative
-    accuracy down the negative tail).  Measured on gfx950 with it, over all 139 cases: at most
+    accuracy down the negative tail).  Measured on gfx950 with it, over 139 cases (these and a
+    since-removed W4 config): at most
     6.0e-4 of a case's outputs differ, every one by one step, the farthest 2.4e-7 from the
     boundary (0.17 E)."""
     from samq import ops
@@ -389,7 +391,7 @@ def test_i8_gemm_refusals(cuda):
     refused("N % 64", lambda o: w8(o, nn=96), cols=96)
     refused("N % BN", lambda o: w8(o, cfg=81, nn=192), cols=192)
     refused("unknown cfg", lambda o: w8(o, cfg=7))
-    for cfg in (85, 86, 93):
+    for cfg in (85, 86, 93):   # 85 / 86: the W4 ping-pong kernel; 93: the id of a removed kernel, unknown
         refused(f"cfg {cfg} on W8", lambda o: w8(o, cfg=cfg))
     wide = torch.zeros((m, 128 + 24), dtype=torch.int8, device=cuda)
     refused("lda % 16", lambda o: w8(o, aa=wide[:, :128]))                       # lda = 152

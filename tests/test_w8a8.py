@@ -9,7 +9,6 @@ a small stated fraction of codes off by one.  Encoder tests state the fraction o
 equal to the golden codes and the max-abs difference in units of the output scale.
 """
 import json
-import os
 
 import numpy as np
 import pytest
@@ -123,7 +122,7 @@ def test_w8a8_gemm_epilogues(cuda, cfg):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("cfg", [0, 81, 82, 83, 85, 86, 93])
+@pytest.mark.parametrize("cfg", [0, 81, 82, 83, 85, 86])
 def test_w4a8_gemm_exact_integer(cuda, cfg):
     """int4 (layout 3, incl. a zero point of 0 -> quirk 4) x int8: integer sums are exact."""
     from oracle import gptq_pack
@@ -206,20 +205,14 @@ def test_w4a8_gemm_grouped(cuda, groupsize, k, cfg):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("m,k,n", [(300, 1280, 512), (8192, 1280, 1280), (520, 5120, 1280), (77, 128, 256),
-                                   (260, 256, 768), (8192, 1280, 5120), (1100, 640, 1408)])
-@pytest.mark.parametrize("cfg", [85, 86, 93] + ([99] if os.environ.get("SAMQ_LIB") == "tuning" else []))
+                                   (260, 256, 768), (8192, 1280, 5120)])
+@pytest.mark.parametrize("cfg", [85, 86])
 def test_w4a8_pingpong_matches_v3(cuda, m, k, n, cfg):
-    """The W4A8 ping-pong kernels (cfg 85; cfg 86 = zero point applied through per-row sums of the
-    int8 activations; cfg 93 = cfg 86 with the LDS-DMA pieces spread through the MFMA bursts) against the v3-style 256x256 kernel (cfg 81): all sum the same int32 products
+    """The W4A8 ping-pong kernel (cfg 85; cfg 86 = zero point applied through per-row sums of the
+    int8 activations) against the 3-slot 256x256 kernel (cfg 81): all sum the same int32 products
     exactly and share the epilogue code, so every epilogue must agree BIT FOR BIT -- ragged M,
     K = 128 (one K tile, shorter than the lookahead), K = 256 (= the lookahead), and the lin2 depth
-    K = 5120.  The weights include zero points of 0..15 (nibble + 1 = 1..16) and saturated codes.
-    With SAMQ_LIB=tuning, cfg 99 (the tile ping-pong, tuning build only) runs the same checks: it
-    needs K >= 512 (shorter K raise NotImplementedError) and is checked with four tiles per
-    workgroup (N = 5120) and an odd tile count (1100 x 1408: 5 x 11 tiles, a last workgroup with one
-    tile), against the 128x128 v3 kernel (cfg 83) where N is not a multiple of 256."""
-    if n % 256 and cfg != 99:
-        pytest.skip("256-column tiles")
+    K = 5120.  The weights include zero points of 0..15 (nibble + 1 = 1..16) and saturated codes."""
     from oracle import gptq_pack
     from samq import ops
     rng = np.random.Generator(np.random.PCG64(m + k + n))
@@ -236,28 +229,24 @@ def test_w4a8_pingpong_matches_v3(cuda, m, k, n, cfg):
     qzd = torch.from_numpy(qz).to(cuda)
     bias = torch.from_numpy(rng.standard_normal(n, dtype=np.float32) * np.float32(0.02)).to(cuda)
     a_s = 0.02
-    if cfg == 99 and k < 512:
-        with pytest.raises(NotImplementedError):
-            ops.w4a8_gemm(a, packed, scf, qzd, n, bias, ops.EPI_BIAS, a_s, 0.0, cfg=cfg)
-        return
     for epi, osc in ((ops.EPI_BIAS, 0.0), (ops.EPI_BIAS_GELU, 0.0), (ops.EPI_F32, 0.0), (ops.EPI_Q8, 0.05),
                      (ops.EPI_Q8_GELU, 0.03)):
-        ref = ops.w4a8_gemm(a, packed, scf, qzd, n, bias, epi, a_s, osc, cfg=81 if n % 256 == 0 else 83)
+        ref = ops.w4a8_gemm(a, packed, scf, qzd, n, bias, epi, a_s, osc, cfg=81)
         got = ops.w4a8_gemm(a, packed, scf, qzd, n, bias, epi, a_s, osc, cfg=cfg)
         assert torch.equal(got, ref), f"epilogue {epi}"
     res0 = torch.from_numpy(rng.standard_normal((m, n), dtype=np.float32)).to(cuda)
-    r81, r85 = res0.clone(), res0.clone()
-    ops.w4a8_gemm(a, packed, scf, qzd, n, bias, ops.EPI_RESADD_F32, a_s, out=r81, cfg=81 if n % 256 == 0 else 83)
-    ops.w4a8_gemm(a, packed, scf, qzd, n, bias, ops.EPI_RESADD_F32, a_s, out=r85, cfg=cfg)
-    assert torch.equal(r85, r81)
+    r81, rpp = res0.clone(), res0.clone()
+    ops.w4a8_gemm(a, packed, scf, qzd, n, bias, ops.EPI_RESADD_F32, a_s, out=r81, cfg=81)
+    ops.w4a8_gemm(a, packed, scf, qzd, n, bias, ops.EPI_RESADD_F32, a_s, out=rpp, cfg=cfg)
+    assert torch.equal(rpp, r81)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("m,k,n", [(300, 1280, 512), (8192, 1280, 1280), (520, 5120, 1280), (8192, 1280, 5120),
                                    (77, 128, 256)])
 def test_w4a8_gemm_rowsums(cuda, m, k, n):
-    """Zero-point row sums from the producer (samq_w4a8_gemm_rs, round 6): with ``rowsum`` = the exact
-    int32 code sums of A the ping-pong GEMMs (cfg 86 / 93 and the automatic pick) give the same bits
+    """Zero-point row sums from the producer (samq_w4a8_gemm_rs): with ``rowsum`` = the exact
+    int32 code sums of A the ping-pong GEMM (cfg 86 and the automatic pick) gives the same bits
     as summing A themselves, on every epilogue; ``rowsum_out`` (int8-code epilogues, any tile
     config) accumulates exactly the row sums of the codes written, on top of what the buffer held."""
     from oracle import gptq_pack
@@ -276,7 +265,7 @@ def test_w4a8_gemm_rowsums(cuda, m, k, n):
     scf = torch.from_numpy(sc.astype(np.float32).reshape(-1)).to(cuda)
     qzd = torch.from_numpy(qz).to(cuda)
     bias = torch.from_numpy(rng.standard_normal(n, dtype=np.float32) * np.float32(0.02)).to(cuda)
-    cfgs = [0] + ([86, 93] if n % 256 == 0 else [])
+    cfgs = [0] + ([86] if n % 256 == 0 else [])
     for cfg in cfgs:
         for epi, osc in ((ops.EPI_BIAS, 0.0), (ops.EPI_BIAS_GELU, 0.0), (ops.EPI_F32, 0.0), (ops.EPI_Q8, 0.05),
                          (ops.EPI_Q8_GELU, 0.03)):
