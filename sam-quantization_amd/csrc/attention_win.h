@@ -30,7 +30,7 @@
 // per ViT-H 2-image launch, fp16 output 1.59e-3 vs 1.95e-3 max-abs from the fp32 oracle, W4A8 store
 // codes off by one 1.7e-3 vs 2.5e-3 (profiles/r4_m.win.log).
 // PHL (round 4, the W4A8 int8-code store): P enters P.V as fp16 hi + lo (P - hi, |P - hi - lo| ~
-// 2^-22 |P|, attention_q8.hip's split) -- two MFMAs per P.V step and for the row sums -- so the
+// 2^-22 |P|, the split of attention_q8_row64.h) -- two MFMAs per P.V step and for the row sums -- so the
 // output carries fp32-level error instead of fp16 P's 2^-12, before the proj QAct's quantiser
 #pragma once
 

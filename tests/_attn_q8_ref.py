@@ -86,7 +86,7 @@ PEAKED_S_OUT = np.float32(0.0371)
 
 
 def lazy_codes(s_a2):
-    """lazyc of csrc/attention_q8.hip (q8_ptab_lazy), in the kernel's fp32 arithmetic."""
+    """lazyc of csrc/attention_q8_util.h (q8_ptab_lazy), in the kernel's fp32 arithmetic."""
     k2 = np.float32(s_a2) * np.float32(1.4426950408889634)
     return int(min(np.floor(np.float32(8.0) / k2), 255))
 

@@ -57,6 +57,39 @@ def test_c_abi_empty_batch_is_a_no_op():
                                   None) == _lib.SAMQ_ERR_INVALID
 
 
+def test_c_abi_rel_attention_q8_argument_checks():
+    """The argument checks of samq_rel_attention_q8_rows and their messages, at both head dims; every case
+    returns before a launch, so this runs without a GPU (kernel and grid choice: the GPU tests)."""
+    from samq import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(16)
+
+    def call(b=1, h=64, w=64, heads=2, hd=64, window=14, s_a2=0.1, row0=0, rows=-1, qkv=p, v16=None):
+        st = lib.samq_rel_attention_q8_rows(qkv, None, p, p, p, b, h, w, heads, hd, window, 0.125, 0.05, 0.08, s_a2,
+                                            0.03, row0, rows, v16, None)
+        return st, lib.samq_last_error().decode()
+
+    assert call(b=0, qkv=None)[0] == 0
+    for kw, code, msg in [
+            (dict(qkv=None), _lib.SAMQ_ERR_INVALID, "rel_attention_q8: null pointer"),
+            (dict(hd=96), _lib.SAMQ_ERR_UNSUPPORTED, "rel_attention_q8: head_dim must be 64 or 80"),
+            (dict(heads=0), _lib.SAMQ_ERR_INVALID, "rel_attention_q8: bad shape"),
+            (dict(s_a2=0.0), _lib.SAMQ_ERR_INVALID, "rel_attention_q8: scales must be > 0"),
+            (dict(qkv=ctypes.c_void_p(8)), _lib.SAMQ_ERR_INVALID, "rel_attention_q8: qkv must be 16-byte aligned"),
+            (dict(row0=60, rows=8), _lib.SAMQ_ERR_INVALID, "rel_attention_q8: bad row range"),
+            (dict(row0=7, rows=14), _lib.SAMQ_ERR_UNSUPPORTED,
+             "rel_attention_q8: a row range must cover whole windows (global: the 64 x 64 grid only)"),
+            (dict(window=0, h=32, w=32, rows=8), _lib.SAMQ_ERR_UNSUPPORTED,
+             "rel_attention_q8: a row range must cover whole windows (global: the 64 x 64 grid only)"),
+            (dict(v16=ctypes.c_void_p(8)), _lib.SAMQ_ERR_INVALID, "rel_attention_q8: v16 must be 16-byte aligned"),
+            (dict(window=17, h=68, w=68), _lib.SAMQ_ERR_UNSUPPORTED, "rel_attention_q8: window must be <= 16"),
+            (dict(window=0, h=65, w=65), _lib.SAMQ_ERR_UNSUPPORTED,
+             "rel_attention_q8: global attention needs H == W <= 64")]:
+        for hd in (64, 80):
+            st, err = call(**{"hd": hd, **kw})
+            assert st == code and msg in err, (kw, hd, st, err)
+
+
 def test_c_abi_rejects_timing_and_layout2_configs():
     """The product library's tile-config table holds exactly ops.W4A16_CFGS: every other id -- the
     tuning build's timing-only variants (70-72, 102, 103) and the ids of retired experiments among
