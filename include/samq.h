@@ -236,6 +236,58 @@ int samq_w8a8_conv_gemm(const int8_t* x, int mode, int B, int Cin, int side, con
 #define SAMQ_Q_OUT_FQ 2
 int samq_quantize(const void* x, void* y, int64_t n, float scale, int flags, hipStream_t stream);
 
+/* ---- int8 activations with zero points (fq_vit asymmetric QActs: the omse observer, uint8
+ * BIT_TYPE_A).  A quantiser is (scale, zp), zp an integer in [-128, 127] (else SAMQ_ERR_INVALID):
+ *   code = clamp(rint(fl(fl(x / s) + zp)), -128, 127),  value = (code - zp) * s
+ * -- the zero point is added to the correctly rounded fp32 quotient BEFORE the round-half-even
+ * (quantizer/uniform.py:31-33).  With every zero point 0 (and col_offset NULL) each entry below is
+ * bit-identical to the entry it extends. */
+
+/* samq_quantize with an output zero point; SAMQ_Q_OUT_FQ gives (code - zp) * scale. */
+int samq_quantize_zp(const void* x, void* y, int64_t n, float scale, int zp, int flags, hipStream_t stream);
+
+/* samq_layernorm_q with zero points: SAMQ_LN_IN_I8 reads x = (code - zp_in) * in_scale (the
+ * subtraction in integers); SAMQ_LN_OUT_I8 writes the codes of (out_scale, zp_out), with
+ * SAMQ_LN_OUT_F32 as well the f32 fake-quant value (code - zp_out) * out_scale. */
+int samq_layernorm_q_zp(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C,
+                        float eps, int flags, float in_scale, float out_scale, int zp_in, int zp_out,
+                        hipStream_t stream);
+
+/* samq_i8_gemm_cfg for W8 weights on activations with zero points; epilogues SAMQ_EPI_Q8 / Q8_GELU /
+ * Q8_RES (any other: SAMQ_ERR_UNSUPPORTED), cfg 0 or a tile config that takes W8 weights:
+ *   y[m,n] = float(sum_k A[m,k] W[n,k] + col_offset[n]) * a_scale * wscale[n] + bias[n]
+ * col_offset int32 [N] or NULL (= 0): the input's zero point as -zp_a * sum_k W[n,k], precomputed per
+ * layer and added in int32 (exact; it nearly cancels against the sum, so it must not be folded into
+ * the float bias).  Q8_RES: residual (R - res_zp) * res_scale, read at row m % rmod when rmod > 0;
+ * mid quantiser (mid_scale > 0) (clamp(rint(y / mid_scale + mid_zp)) - mid_zp) * mid_scale; every
+ * output quantiser (out_scale, out_zp). */
+int samq_i8_gemm_zp(const int8_t* A, int64_t lda, const int8_t* wpacked, const float* wscale, const float* bias,
+                    void* C, int64_t ldc, const int8_t* R, int64_t ldr, int M, int N, int K, int epilogue,
+                    float a_scale, float mid_scale, float res_scale, float out_scale, int cfg,
+                    const int32_t* col_offset, int mid_zp, int res_zp, int out_zp, int rmod, hipStream_t stream);
+
+/* samq_w8a8_conv_gemm on activations with zero points (arguments as samq_i8_gemm_zp).  pad16 (mode 2,
+ * required there; 16-byte aligned): 16 device bytes, each the code of the input's zero point -- the
+ * 3x3 gather reads them outside the map (a padded value of 0.0 is the code zp, not the code 0), so
+ * col_offset holds for border pixels as well. */
+int samq_w8a8_conv_gemm_zp(const int8_t* x, int mode, int B, int Cin, int side, const int8_t* wpacked,
+                           const float* wscale, const float* bias, void* C, const int8_t* R, int rmod, int N,
+                           int epilogue, float a_scale, float mid_scale, float res_scale, float out_scale,
+                           const int32_t* col_offset, int mid_zp, int res_zp, int out_zp, const int8_t* pad16,
+                           hipStream_t stream);
+
+/* samq_rel_attention_q8_rows on codes with zero points: qkv codes (s_qkv, zp_qkv), the two score
+ * quantisers (s_a1, zp_a1) / (s_a2, zp_a2), output codes (s_out, zp_out).  q.k is
+ * sum_d (q - zp_qkv)(k - zp_qkv), exact in int32; the rel-pos terms take (q - zp_qkv) s_qkv; the
+ * output is softmax . ((v - zp_qkv) s_qkv).  Pad tokens of a window: the codes of qkv_bias under
+ * (s_qkv, zp_qkv), or the code zp_qkv (the value 0.0) when qkv_bias is NULL.  v16 must be NULL
+ * (SAMQ_ERR_UNSUPPORTED otherwise): the 64 x 64 kernel runs its int8-V form. */
+int samq_rel_attention_q8_zp(const int8_t* qkv, const float* qkv_bias, const float* rel_pos_h,
+                             const float* rel_pos_w, int8_t* out, int B, int H, int W, int heads, int hd,
+                             int window, float sm_scale, float s_qkv, float s_a1, float s_a2, float s_out,
+                             int row0, int rows, const void* v16, int zp_qkv, int zp_a1, int zp_a2, int zp_out,
+                             hipStream_t stream);
+
 /* Running min / max of a calibration tensor viewed as (rows, C) row-major -- fq_vit
  * MinmaxObserver.update (observer/minmax.py:14-29, reshape_tensor observer/base.py:16-29):
  *   SAMQ_MM_PER_ROW: one value per row     (conv / linear weights, v.reshape(out, -1));

@@ -98,6 +98,76 @@ extern "C" int samq_rel_attention_q8_rows(const int8_t* qkv, const float* qkv_bi
   return SAMQ_OK;
 }
 
+// The same on codes with zero points (AttnQ8ParamsZp, attention_q8_util.h): the ZP instantiation of
+// every kernel above.  No fp16 V copy: the row64 kernel runs its int8-V form.
+extern "C" int samq_rel_attention_q8_zp(const int8_t* qkv, const float* qkv_bias, const float* rel_pos_h,
+                                        const float* rel_pos_w, int8_t* out, int B, int H, int W, int heads, int hd,
+                                        int window, float sm_scale, float s_qkv, float s_a1, float s_a2, float s_out,
+                                        int row0, int rows, const void* v16, int zp_qkv, int zp_a1, int zp_a2,
+                                        int zp_out, hipStream_t stream) {
+  if (B == 0) return SAMQ_OK;   // empty batch: no work, data pointers may be null
+  SAMQ_REQUIRE(qkv && rel_pos_h && rel_pos_w && out, SAMQ_ERR_INVALID, "rel_attention_q8_zp: null pointer");
+  SAMQ_REQUIRE(hd == 64 || hd == 80, SAMQ_ERR_UNSUPPORTED, "rel_attention_q8_zp: head_dim must be 64 or 80");
+  SAMQ_REQUIRE(!v16, SAMQ_ERR_UNSUPPORTED, "rel_attention_q8_zp: no fp16 V copy under zero points (pass null)");
+  SAMQ_REQUIRE(B > 0 && H > 0 && W > 0 && heads > 0, SAMQ_ERR_INVALID, "rel_attention_q8_zp: bad shape");
+  SAMQ_REQUIRE(s_qkv > 0.f && s_a1 > 0.f && s_a2 > 0.f && s_out > 0.f, SAMQ_ERR_INVALID,
+               "rel_attention_q8_zp: scales must be > 0");
+  auto zok = [](int z) { return z >= -128 && z <= 127; };
+  SAMQ_REQUIRE(zok(zp_qkv) && zok(zp_a1) && zok(zp_a2) && zok(zp_out), SAMQ_ERR_INVALID,
+               "rel_attention_q8_zp: zero points must be in [-128, 127]");
+  SAMQ_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 3) == 0, SAMQ_ERR_INVALID,
+               "rel_attention_q8_zp: qkv must be 16-byte aligned");
+  if (rows < 0) { row0 = 0; rows = H; }   // the whole grid
+  SAMQ_REQUIRE(row0 >= 0 && rows > 0 && row0 + rows <= H, SAMQ_ERR_INVALID, "rel_attention_q8_zp: bad row range");
+  SAMQ_REQUIRE(window > 0 ? (row0 % window == 0 && (rows % window == 0 || row0 + rows == H))
+                          : (rows == H || H == 64), SAMQ_ERR_UNSUPPORTED,
+               "rel_attention_q8_zp: a row range must cover whole windows (global: the 64 x 64 grid only)");
+  AttnQ8ParamsZp p{};
+  p.qkv = qkv; p.qkv_bias = qkv_bias; p.relh = rel_pos_h; p.relw = rel_pos_w; p.out = out;
+  p.v16 = nullptr;
+  p.B = B; p.H = H; p.W = W; p.heads = heads; p.C = heads * hd;
+  p.qk_scale = (s_qkv * sm_scale) * s_qkv;
+  p.s_qkv = s_qkv; p.s_a1 = s_a1; p.s_a2 = s_a2; p.s_out = s_out;
+  p.inv_a1 = 1.0f / s_a1; p.inv_a2 = 1.0f / s_a2; p.k2 = s_a2 * 1.4426950408889634f;
+  p.z_qkv = (float)zp_qkv; p.z_a1 = (float)zp_a1; p.z_a2 = (float)zp_a2; p.z_out = (float)zp_out;
+  p.zfold = (float)zp_a2 - (float)zp_a1 * (s_a1 * p.inv_a2);
+  p.zi_qkv = zp_qkv; p.dz2 = hd * zp_qkv * zp_qkv;
+  p.zc_twice = zp_qkv == -128;
+  p.zc = (int)(0x01010101u * (uint32_t)((p.zc_twice ? 64 : -zp_qkv) & 0xFF));
+  if (window > 0) {
+    SAMQ_REQUIRE(window <= 16, SAMQ_ERR_UNSUPPORTED, "rel_attention_q8_zp: window must be <= 16");
+    p.S = window; p.window = window;
+    p.nwh = (rows + window - 1) / window; p.nww = (W + window - 1) / window;
+    p.row0 = row0 / window;
+    p.L = window * window;
+  } else {
+    SAMQ_REQUIRE(H == W && H <= 64, SAMQ_ERR_UNSUPPORTED, "rel_attention_q8_zp: global attention needs H == W <= 64");
+    p.S = H; p.window = 0; p.nwh = p.nww = 1; p.L = H * W;
+    p.row0 = row0;
+  }
+  with_head_dim(hd, [&](auto hdc) {
+    constexpr int D = decltype(hdc)::value;
+    constexpr int NWQ = 4;
+    const unsigned items = B * p.nwh * p.nww;
+    if (window == 14)
+      hipLaunchKernelGGL((rel_attention_q8_win_kernel<D, 14, 7, true>), dim3(items, heads, 2), dim3(64 * 7), 0, stream, p);
+    else if (window > 0 && p.L <= 13 * 16)
+      hipLaunchKernelGGL((rel_attention_q8_kernel<D, true, 13, 256, 16, true>), dim3(items, heads, 1), dim3(64 * 13), 0,
+                         stream, p);
+    else if (window > 0)
+      hipLaunchKernelGGL((rel_attention_q8_kernel<D, true, 16, 256, 16, true>), dim3(items, heads, 1), dim3(64 * 16), 0,
+                         stream, p);
+    else if (H != 64)
+      hipLaunchKernelGGL((rel_attention_q8_kernel<D, false, NWQ, 64, 64, true>),
+                         dim3(B, heads, (p.L + 16 * NWQ - 1) / (16 * NWQ)), dim3(64 * NWQ), 0, stream, p);
+    else
+      hipLaunchKernelGGL((rel_attention_q8_row64_kernel<D, NWQ, false, true>), dim3(B, heads, rows), dim3(64 * NWQ), 0,
+                         stream, p);
+  });
+  SAMQ_LAUNCH_CHECK("rel_attention_q8_zp launch");
+  return SAMQ_OK;
+}
+
 extern "C" int samq_rel_attention_q8(const int8_t* qkv, const float* qkv_bias, const float* rel_pos_h,
                                      const float* rel_pos_w, int8_t* out, int B, int H, int W, int heads, int hd,
                                      int window, float sm_scale, float s_qkv, float s_a1, float s_a2, float s_out,

@@ -18,8 +18,8 @@
 
 namespace samq {
 
-template <int D, bool RESIDENT, int NWQ, int KC, int MAXS>
-__global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params p) {
+template <int D, bool RESIDENT, int NWQ, int KC, int MAXS, bool ZP = false>
+__global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(typename AttnQ8ParamsOf<ZP>::type p) {
   static_assert(D == 64 || D == 80, "head dim");
   constexpr int QD = D, KPITCH = q8_kpitch<D>();
   constexpr int PARTS = D / 16;                  // 16-byte pieces per token and head
@@ -75,6 +75,9 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
         if (inimg) {
           kc = *(const u32x4*)(tp + C + head * QD + part * 16);
           vc = *(const u32x4*)(tp + 2 * C + head * QD + part * 16);
+        } else if constexpr (ZP) {   // pad token: the codes of the bias, or of 0.0
+          kc = q8_zp_pad16(p.qkv_bias ? p.qkv_bias + C + head * QD + part * 16 : nullptr, p.s_qkv, p.z_qkv);
+          vc = q8_zp_pad16(p.qkv_bias ? p.qkv_bias + 2 * C + head * QD + part * 16 : nullptr, p.s_qkv, p.z_qkv);
         } else if (p.qkv_bias) {
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
@@ -87,8 +90,11 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
       }
       *(u32x4*)(&k_lds[buf][key * KPITCH + part * 16]) = kc;
 #pragma unroll
-      for (int e = 0; e < 16; ++e)
-        vt_lds[buf][(part * 16 + e) * VTP + key] = (_Float16)(float)(int8_t)((vc[e >> 2] >> (8 * (e & 3))) & 0xFFu);
+      for (int e = 0; e < 16; ++e) {
+        float vf = (float)(int8_t)((vc[e >> 2] >> (8 * (e & 3))) & 0xFFu);
+        if constexpr (ZP) vf -= p.z_qkv;   // V as v - z (exact in fp16)
+        vt_lds[buf][(part * 16 + e) * VTP + key] = (_Float16)vf;
+      }
     }
   };
 
@@ -142,7 +148,9 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
           const float4_t w4 = *(const float4_t*)(tw + d4 * 16 + e4 * 4);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float qf = (float)(int8_t)((cw[e4] >> (8 * e)) & 0xFFu) * p.s_qkv;
+            float qf = (float)(int8_t)((cw[e4] >> (8 * e)) & 0xFFu);
+            if constexpr (ZP) qf -= p.z_qkv;   // code - z: exact
+            qf *= p.s_qkv;
             ah = fmaf(qf, h4[e], ah);
             aw = fmaf(qf, w4[e], aw);
           }
@@ -161,6 +169,8 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
   const float* rhq = &rh_lds[wave][ql * (MAXS + 1)];
   const float* rwq = &rw_lds[wave][ql * (MAXS + 1)];
   const float inv1 = p.inv_a1, inv2 = p.inv_a2, sa1 = p.s_a1;
+  int4v zseed = {0, 0, 0, 0};
+  if constexpr (ZP) zseed = q8_zp_seed(p, qfrag, qtail);
 
   if (RESIDENT) {
     for (int c0 = 0; c0 < L; c0 += KC) stage(c0, 0);   // KC >= L: one pass
@@ -179,7 +189,11 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
 #pragma unroll
     for (int bb = 0; bb < 4; ++bb) {
       const int4v kf = *(const int4v*)(&k_lds[buf][(koff + bb * 16 + ql) * KPITCH + g * 16]);
-      const int4v z = {0, 0, 0, 0};
+      int4v z = {0, 0, 0, 0};
+      if constexpr (ZP) {
+        z = q8_zp_ksum(p, kf, zseed);
+        if constexpr (D == 80) z = q8_zp_ksum(p, q8_tail(&k_lds[buf][(koff + bb * 16 + qlt) * KPITCH], g), z);
+      }
       int4v st = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qfrag, z, 0, 0, 0);
       if constexpr (D == 80)
         st = __builtin_amdgcn_mfma_i32_16x16x64_i8(q8_tail(&k_lds[buf][(koff + bb * 16 + qlt) * KPITCH], g), qtail, st,
@@ -192,9 +206,15 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
           int kh, kw;
           tok(key, kh, kw);
           const float v = (float)st[i] * p.qk_scale;
+          if constexpr (ZP) {   // rint(x / s + z), value (code - z) s; the softmax below works on code differences
+            const float v1 = (fminf(fmaxf(__builtin_rintf(v * inv1 + p.z_a1), -128.f), 127.f) - p.z_a1) * sa1;
+            const float t = (v1 + rhq[kh]) + rwq[kw];
+            c = fminf(fmaxf(__builtin_rintf(t * inv2 + p.z_a2), -128.f), 127.f);
+          } else {
           const float v1 = fminf(fmaxf(__builtin_rintf(v * inv1), -128.f), 127.f) * sa1;
           const float t = (v1 + rhq[kh]) + rwq[kw];
           c = fminf(fmaxf(__builtin_rintf(t * inv2), -128.f), 127.f);
+          }
         }
         c2[bb][i] = c;
         cmax = fmaxf(cmax, c);
@@ -254,6 +274,11 @@ __global__ __launch_bounds__(64 * NWQ) void rel_attention_q8_kernel(AttnQ8Params
       uint32_t w = 0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
+        if constexpr (ZP) {
+          const float o = acc[t][i] / lsum * p.s_qkv;
+          w |= ((uint32_t)(int)q8_exact_zp(o, p.s_out, 1.0f / p.s_out, p.z_out) & 0xFFu) << (8 * i);
+          continue;
+        }
         const float o = acc[t][i] / lsum * p.s_qkv;
         w |= ((uint32_t)(int)aq8(o, p.s_out) & 0xFFu) << (8 * i);
       }

@@ -33,9 +33,10 @@
 
 namespace samq {
 
-template <int D, int NWQ, bool V16 = false>
-__global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(AttnQ8Params p) {
+template <int D, int NWQ, bool V16 = false, bool ZP = false>
+__global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(typename AttnQ8ParamsOf<ZP>::type p) {
   static_assert(D == 64 || D == 80, "head dim");
+  static_assert(!(ZP && V16), "zero points: int8 V only");
   constexpr int QD = D;
   constexpr int G = 64, KC = 64;
   constexpr int KP = Q8_KP, VP = Q8_VP;
@@ -109,7 +110,8 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
         *(u32x4*)(&k_lds[buf][lane * KP + 64]) = treg[r];
       } else if (wave == 1) {
         half8_t h0, h1;
-        q8_unpack16(treg[r], h0, h1);
+        if constexpr (ZP) q8_unpack16_zp(treg[r], h0, h1, p.z_qkv);
+        else q8_unpack16(treg[r], h0, h1);
         *(half8_t*)(&v_lds[buf][lane * VP + 64]) = h0;
         *(half8_t*)(&v_lds[buf][lane * VP + 64 + 8]) = h1;
       }
@@ -123,7 +125,8 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
         *(u32x4*)(&v_lds[buf][key * VP + part * 16 + 8]) = vreg[r][2 * j + 1];
       } else {
         half8_t h0, h1;
-        q8_unpack16(vreg[r][j], h0, h1);
+        if constexpr (ZP) q8_unpack16_zp(vreg[r][j], h0, h1, p.z_qkv);   // V as v - z
+        else q8_unpack16(vreg[r][j], h0, h1);
         *(half8_t*)(&v_lds[buf][key * VP + part * 16]) = h0;
         *(half8_t*)(&v_lds[buf][key * VP + part * 16 + 8]) = h1;
       }
@@ -147,7 +150,8 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
 #pragma unroll
   for (int bb = 0; bb < 4; ++bb) {
     float4_t rh4, rw4;
-    q8_rel_block<D>(p, &q_lds[wave][ql * KP], qy, G, bb, lane, rh4, rw4);
+    if constexpr (ZP) q8_rel_block<D, true>(p, &q_lds[wave][ql * KP], qy, G, bb, lane, rh4, rw4, p.z_qkv);
+    else q8_rel_block<D>(p, &q_lds[wave][ql * KP], qy, G, bb, lane, rh4, rw4);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       rh_lds[wave][ql * (G + 1) + 16 * bb + 4 * g + i] = rh4[i];
@@ -163,6 +167,14 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
   for (int bb = 0; bb < 4; ++bb)
 #pragma unroll
     for (int i = 0; i < 4; ++i) rwr[bb][i] *= inv2;
+  int4v zseed = {0, 0, 0, 0};
+  if constexpr (ZP) {
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) rwr[bb][i] += p.zfold;
+    zseed = q8_zp_seed(p, qfrag, qtail);
+  }
   const float lazy = (float)lazyc;
   const int trow = ql >> 2, tcol = 4 * (ql & 3);
   const half8_t ones = {1, 1, 1, 1, 1, 1, 1, 1};
@@ -182,12 +194,19 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
 #pragma unroll
     for (int bb = 0; bb < 4; ++bb) {
       const int4v kf = *(const int4v*)(&k_lds[buf][(bb * 16 + ql) * KP + g * 16]);
-      const int4v z = {0, 0, 0, 0};
+      int4v z = {0, 0, 0, 0};
+      if constexpr (ZP) {
+        z = q8_zp_ksum(p, kf, zseed);
+        if constexpr (D == 80) z = q8_zp_ksum(p, q8_tail(&k_lds[buf][(bb * 16 + qlt) * KP], g), z);
+      }
       int4v st = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qfrag, z, 0, 0, 0);
       if constexpr (D == 80)
         st = __builtin_amdgcn_mfma_i32_16x16x64_i8(q8_tail(&k_lds[buf][(bb * 16 + qlt) * KP], g), qtail, st, 0, 0, 0);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) c[bb][i] = q8_score(st[i], c1, k12, rh_row, rwr[bb][i]);
+      for (int i = 0; i < 4; ++i) {
+        if constexpr (ZP) c[bb][i] = q8_score_zp(st[i], c1, p.z_a1, k12, rh_row, rwr[bb][i]);
+        else c[bb][i] = q8_score(st[i], c1, k12, rh_row, rwr[bb][i]);
+      }
     }
     const float cmax = max_rows4(q8_max16(c));
     if (cmax > m + lazy) {   // per query column: move the offset, rescale O and l
@@ -230,6 +249,11 @@ __global__ __launch_bounds__(64 * NWQ, 3) void rel_attention_q8_row64_kernel(Att
     uint32_t w = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+      if constexpr (ZP) {
+        const float o = acc[t][i] / lsum * p.s_qkv;
+        w |= ((uint32_t)(int)q8_exact_zp(o, p.s_out, 1.0f / p.s_out, p.z_out) & 0xFFu) << (8 * i);
+        continue;
+      }
       const float o = acc[t][i] / lsum * p.s_qkv;
       w |= ((uint32_t)(int)aq8(o, p.s_out) & 0xFFu) << (8 * i);
     }

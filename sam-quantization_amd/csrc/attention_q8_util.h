@@ -25,7 +25,67 @@ struct AttnQ8Params {
   float inv_a1, inv_a2, k2;   // 1/s_a1, 1/s_a2, s_a2*log2(e)
 };
 
+// Activations with zero points (samq_rel_attention_q8_zp): the kernels instantiated with ZP take this
+// struct instead; the symmetric kernels keep AttnQ8Params and with it their argument layout.  With
+// z = zp_qkv, codes q, k, v and D the head dim:
+//   q.k    sum_d (q - z)(k - z) = sum q k + (-z) sum_d k - z sum_d q + D z^2, all on the int8 MFMA: the
+//          accumulator tile is seeded with this lane's query constant D z^2 - z sum_d q (q8_zp_seed) and
+//          a second v_mfma_i32_16x16x64_i8 of the same K fragment against the constant operand -z in
+//          every byte adds (-z) sum_d k of each key -- no per-score VALU work and no key sums in LDS
+//          (these loops are VALU-bound; the MFMA pipe has the room).  -z = 128 (z = -128) does not fit a
+//          byte: the operand is then 64 and the MFMA runs twice (zc_twice).
+//   rel    the query codes are unpacked to fp16 as q - z (exact: |q - z| <= 255).
+//   scores code1 = clamp(rint(st c1 + z1)), code2 = clamp(rint((code1 - z1) k12 + (rel_h + rel_w) /
+//          s_a2 + z2)) = clamp(rint(fma(code1, k12, rh + rw + zfold))), zfold = z2 - z1 k12 folded into
+//          the per-lane rel_w registers.  The softmax is shift-invariant and the P table works on code
+//          differences d = c - m in [-255, lazyc], codes still in [-128, 127]: nothing else changes.
+//   P.V    V is staged as v - z (exact in fp16), so O / l s_qkv is the output value as before, then the
+//          output quantiser with z_out.  (O - z l on the raw codes cancels: on the 4096 keys of the
+//          64 x 64 grid the fp32 accumulation error of sum P v, ~1e-4 of |z|, is 1e-3 of an output code
+//          at a fine s_out -- 1.75e-4 of the codes of the exact-tie test moved.)
+//   pads   tokens outside the image: clamp(rint(bias / s + z)), or the code z without a bias.
+struct AttnQ8ParamsZp : AttnQ8Params {
+  float z_qkv, z_a1, z_a2, z_out, zfold;
+  int zi_qkv, dz2;          // z as int; D z^2
+  int zc;                   // the constant B operand: -z (64 for z = -128) in every byte
+  int zc_twice;             // z = -128: the constant MFMA runs twice
+};
+template <bool ZP> struct AttnQ8ParamsOf { typedef AttnQ8Params type; };
+template <> struct AttnQ8ParamsOf<true> { typedef AttnQ8ParamsZp type; };
+
 typedef int int4v __attribute__((ext_vector_type(4)));
+
+// sum_d q[d] over a lane's 16 (+ 16 tail) query codes, reduced over the four lane groups that share a
+// query, into the accumulator seed D z^2 - z sum_d q of that query's column
+__device__ __forceinline__ int4v q8_zp_seed(const AttnQ8ParamsZp& p, int4v qfrag, int4v qtail) {
+  int s = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    s = __builtin_amdgcn_sdot4(qfrag[e], 0x01010101, s, false);
+    s = __builtin_amdgcn_sdot4(qtail[e], 0x01010101, s, false);   // zero at D = 64 and in lane groups 1..3
+  }
+  s += __shfl_xor(s, 16, 64);
+  s += __shfl_xor(s, 32, 64);
+  const int cq = p.dz2 - p.zi_qkv * s;
+  return int4v{cq, cq, cq, cq};
+}
+// seed + (-z) sum_d k of the 16 keys of K fragment kf (wave-uniform branch for z = -128)
+__device__ __forceinline__ int4v q8_zp_ksum(const AttnQ8ParamsZp& p, int4v kf, int4v acc) {
+  const int4v c = {p.zc, p.zc, p.zc, p.zc};
+  acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, c, acc, 0, 0, 0);
+  if (p.zc_twice) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, c, acc, 0, 0, 0);
+  return acc;
+}
+// pad-token codes under a zero point: 16 codes of bias[0..15] (null: the code z) as four dwords
+__device__ __forceinline__ u32x4 q8_zp_pad16(const float* bias, float s, float z) {
+  u32x4 w = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int c = (int)(bias ? q8_exact_zp(bias[e], s, 1.0f / s, z) : z);
+    w[e >> 2] |= ((uint32_t)c & 0xFFu) << (8 * (e & 3));
+  }
+  return w;
+}
 
 // LDS pitches of the row64 and window kernels.  K rows at 96 bytes: the ds_read_b128 fragment reads
 // (16 rows x 16 bytes per lane group) are conflict-free in all four lane groups -- at 80 bytes three lane
@@ -71,6 +131,15 @@ __device__ __forceinline__ void q8_unpack16(u32x4 w, half8_t& h0, half8_t& h1) {
   }
 }
 
+// q8_unpack16 as code - z (zero-point kernels: V staged as v - z; exact in fp16)
+__device__ __forceinline__ void q8_unpack16_zp(u32x4 w, half8_t& h0, half8_t& h1, float z) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    h0[e] = (_Float16)((float)(int8_t)((w[e >> 2] >> (8 * (e & 3))) & 0xFFu) - z);
+    h1[e] = (_Float16)((float)(int8_t)((w[2 + (e >> 2)] >> (8 * (e & 3))) & 0xFFu) - z);
+  }
+}
+
 // 8 int8 codes -> fp16 (exact); MASKED: all zero unless ``on``
 template <bool MASKED>
 __device__ __forceinline__ half8_t q8_unpack8(uint2 cw, bool on) {
@@ -78,6 +147,17 @@ __device__ __forceinline__ half8_t q8_unpack8(uint2 cw, bool on) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const _Float16 v = (_Float16)(float)(int8_t)((((e < 4) ? cw.x : cw.y) >> (8 * (e & 3))) & 0xFFu);
+    qb[e] = MASKED ? (on ? v : (_Float16)0.f) : v;
+  }
+  return qb;
+}
+// the same as code - z (zero-point kernels; exact in fp16: |code - z| <= 255)
+template <bool MASKED>
+__device__ __forceinline__ half8_t q8_unpack8_zp(uint2 cw, bool on, float z) {
+  half8_t qb;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const _Float16 v = (_Float16)((float)(int8_t)((((e < 4) ? cw.x : cw.y) >> (8 * (e & 3))) & 0xFFu) - z);
     qb[e] = MASKED ? (on ? v : (_Float16)0.f) : v;
   }
   return qb;
@@ -97,9 +177,10 @@ template <int D> constexpr int q8_kpitch() { return D == 64 ? 80 : Q8_KP; }
 // hold dims 64 + 8 g .. + 7, groups 2 / 3 read what 0 / 1 read and zero it in BOTH operands (a table
 // value times a zero code would still be NaN for an Inf) -- rather than a 16x16x16: one opcode along
 // the accumulate chain (see q8_tail).
-template <int D>
+// ZP: the codes enter as code - zq (q8_unpack8_zp).
+template <int D, bool ZP = false>
 __device__ __forceinline__ void q8_rel_block(const AttnQ8Params& p, const int8_t* qcodes_lane, int qy, int side,
-                                             int bb, int lane, float4_t& rh4, float4_t& rw4) {
+                                             int bb, int lane, float4_t& rh4, float4_t& rw4, float zq = 0.f) {
   const int ql = lane & 15, g = lane >> 4;
   int r = qy - (16 * bb + ql) + side - 1;      // table row of this lane's A row (kk = 16 bb + ql)
   r = r < 0 ? 0 : (r > 2 * side - 2 ? 2 * side - 2 : r);   // rows past the window: any valid row (masked)
@@ -108,7 +189,9 @@ __device__ __forceinline__ void q8_rel_block(const AttnQ8Params& p, const int8_t
 #pragma unroll
   for (int s = 0; s < D / 32; ++s) {
     const uint2 cw = *(const uint2*)(qcodes_lane + 32 * s + 8 * g);   // codes of query ql, dims 32s+8g..+7
-    const half8_t qb = q8_unpack8<false>(cw, true);
+    half8_t qb;
+    if constexpr (ZP) qb = q8_unpack8_zp<false>(cw, true, zq);
+    else qb = q8_unpack8<false>(cw, true);
 #pragma unroll
     for (int tab = 0; tab < 2; ++tab) {
       const float* src = (tab ? p.relw : p.relh) + (int64_t)r * D + 32 * s + 8 * g;
@@ -130,7 +213,9 @@ __device__ __forceinline__ void q8_rel_block(const AttnQ8Params& p, const int8_t
     const bool on = g < 2;
     const int toff = T0 + 8 * (g & 1);          // groups 2 / 3 read what 0 / 1 read, and zero it
     const uint2 cw = *(const uint2*)(qcodes_lane + toff);
-    const half8_t qb = q8_unpack8<true>(cw, on);
+    half8_t qb;
+    if constexpr (ZP) qb = q8_unpack8_zp<true>(cw, on, zq);
+    else qb = q8_unpack8<true>(cw, on);
 #pragma unroll
     for (int tab = 0; tab < 2; ++tab) {
       const float* src = (tab ? p.relw : p.relh) + (int64_t)r * D + toff;
@@ -206,6 +291,13 @@ constexpr int Q8_MAGB = 0x4B400000;
 // here, after q1: summed at the call site, the compiler schedules the score loops differently.
 __device__ __forceinline__ float q8_score(int st, float c1, float k12, float rh, float rw) {
   const float q1 = __builtin_amdgcn_fmed3f(__builtin_rintf((float)st * c1), -128.f, 127.f);
+  return __builtin_amdgcn_fmed3f(fmaf(q1, k12, rh + rw) + Q8_MAG, Q8_MAG - 128.f, Q8_MAG + 127.f);
+}
+
+// q8_score with the zero points z1 (first quantiser) and, folded into rw by the caller together with
+// -z1 k12, z2: code1 = clamp(rint(st c1 + z1)), code2 = clamp(rint(fma(code1, k12, rh + rw)))
+__device__ __forceinline__ float q8_score_zp(int st, float c1, float z1, float k12, float rh, float rw) {
+  const float q1 = __builtin_amdgcn_fmed3f(__builtin_rintf(fmaf((float)st, c1, z1)), -128.f, 127.f);
   return __builtin_amdgcn_fmed3f(fmaf(q1, k12, rh + rw) + Q8_MAG, Q8_MAG - 128.f, Q8_MAG + 127.f);
 }
 

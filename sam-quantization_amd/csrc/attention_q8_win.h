@@ -21,9 +21,9 @@
 
 namespace samq {
 
-template <int D, int SW, int NWQ = SW>
+template <int D, int SW, int NWQ = SW, bool ZP = false>
 // two workgroups per CU: LDS <= 80 KiB and (HIP's second bound = waves per SIMD) <= 512 / (waves / 2) VGPRs
-__global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_win_kernel(AttnQ8Params p) {
+__global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_win_kernel(typename AttnQ8ParamsOf<ZP>::type p) {
   static_assert(D == 64 || D == 80, "head dim");
   constexpr int QD = D, PARTS = D / 16;                   // 16-byte pieces per token and head
   constexpr int SLOTS = 16 * SW, KP = Q8_KP, VP = Q8_VP;
@@ -64,6 +64,9 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
       if (inimg) {
         kc = *(const u32x4*)(tp + C + head * QD + part * 16);
         vc = *(const u32x4*)(tp + 2 * C + head * QD + part * 16);
+      } else if constexpr (ZP) {   // pad token: the codes of the bias, or of 0.0
+        kc = q8_zp_pad16(p.qkv_bias ? p.qkv_bias + C + head * QD + part * 16 : nullptr, p.s_qkv, p.z_qkv);
+        vc = q8_zp_pad16(p.qkv_bias ? p.qkv_bias + 2 * C + head * QD + part * 16 : nullptr, p.s_qkv, p.z_qkv);
       } else if (p.qkv_bias) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -76,10 +79,14 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
     }
     *(u32x4*)(&k_lds[slot * KP + part * 16]) = kc;
     half8_t h0, h1;
+    if constexpr (ZP) {
+      q8_unpack16_zp(vc, h0, h1, p.z_qkv);   // V as v - z
+    } else {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       h0[e] = (_Float16)(float)(int8_t)((vc[e >> 2] >> (8 * (e & 3))) & 0xFFu);
       h1[e] = (_Float16)(float)(int8_t)((vc[2 + (e >> 2)] >> (8 * (e & 3))) & 0xFFu);
+    }
     }
     *(half8_t*)(&v_lds[slot * VP + part * 16]) = h0;
     *(half8_t*)(&v_lds[slot * VP + part * 16 + 8]) = h1;
@@ -113,7 +120,8 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
   float rwr[4];
   {
     float4_t rh4, rw4;
-    q8_rel_block<D>(p, &q_lds[wave][ql * KP], qy, SW, 0, lane, rh4, rw4);
+    if constexpr (ZP) q8_rel_block<D, true>(p, &q_lds[wave][ql * KP], qy, SW, 0, lane, rh4, rw4, p.z_qkv);
+    else q8_rel_block<D>(p, &q_lds[wave][ql * KP], qy, SW, 0, lane, rh4, rw4);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       rwr[i] = rw4[i];
@@ -131,6 +139,12 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
   const float c1 = p.qk_scale * p.inv_a1, inv2 = p.inv_a2, k2 = p.k2, k12 = p.s_a1 * p.inv_a2;
 #pragma unroll
   for (int i = 0; i < 4; ++i) rwr[i] *= inv2;
+  int4v zseed = {0, 0, 0, 0};
+  if constexpr (ZP) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rwr[i] += p.zfold;
+    zseed = q8_zp_seed(p, qfrag, qtail);
+  }
   const float lazy = (float)lazyc;
   constexpr float MASKC = Q8_MAG - 400.f;        // masked slots: a table entry below PTABW_BASE - 255, P = 0
   uint32_t tbase = 0;
@@ -156,13 +170,19 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
       const int kh = 4 * ch + bb;
       const float rh_row = rhq[kh] * inv2;
       const int4v kf = *(const int4v*)(&k_lds[(kh * 16 + ql) * KP + g * 16]);
-      const int4v z = {0, 0, 0, 0};
+      int4v z = {0, 0, 0, 0};
+      if constexpr (ZP) {
+        z = q8_zp_ksum(p, kf, zseed);
+        if constexpr (D == 80) z = q8_zp_ksum(p, q8_tail(&k_lds[(kh * 16 + qlt) * KP], g), z);
+      }
       int4v st = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qfrag, z, 0, 0, 0);
       if constexpr (D == 80)
         st = __builtin_amdgcn_mfma_i32_16x16x64_i8(q8_tail(&k_lds[(kh * 16 + qlt) * KP], g), qtail, st, 0, 0, 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float cq = q8_score(st[i], c1, k12, rh_row, rwr[i]);
+        float cq;
+        if constexpr (ZP) cq = q8_score_zp(st[i], c1, p.z_a1, k12, rh_row, rwr[i]);
+        else cq = q8_score(st[i], c1, k12, rh_row, rwr[i]);
         c[bb][i] = 4 * g + i < SW ? cq : MASKC;
       }
     }
@@ -207,6 +227,11 @@ __global__ __launch_bounds__(64 * NWQ, (2 * NWQ + 3) / 4) void rel_attention_q8_
       uint32_t w = 0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
+        if constexpr (ZP) {
+          const float o = acc[t][i] / lsum * p.s_qkv;
+          w |= ((uint32_t)(int)q8_exact_zp(o, p.s_out, 1.0f / p.s_out, p.z_out) & 0xFFu) << (8 * i);
+          continue;
+        }
         const float o = acc[t][i] / lsum * p.s_qkv;
         w |= ((uint32_t)(int)aq8(o, p.s_out) & 0xFFu) << (8 * i);
       }

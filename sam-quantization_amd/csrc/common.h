@@ -186,6 +186,27 @@ __device__ __forceinline__ float2_t q8_exact2(float2_t v, float s, float inv, fl
   return float2_t{__builtin_amdgcn_fmed3f(__builtin_rintf(q2.x), -128.f, 127.f),
                   __builtin_amdgcn_fmed3f(__builtin_rintf(q2.y), -128.f, 127.f)};
 }
+// The quantisers with a zero point (fq_vit quantizer/uniform.py:31-33): clamp(rint(fl(fl(v / s) + zp)),
+// -128, 127) -- the zero point (an integer in [-128, 127], as a float) is added to the correctly rounded
+// quotient BEFORE the rounding: rint(q) + zp differs at exact ties when zp is odd.  Same chains as
+// q8_exact / q8_exact2 (zp == 0 gives their bits); the pair form wants lim >= 256.5 s, since a
+// quotient of -255.5 still rounds into the code range under zp = 127.
+__device__ __forceinline__ float q8_exact_zp(float v, float s, float inv, float zp) {
+  const float q = v * inv;
+  const float q1 = __builtin_fmaf(__builtin_fmaf(-q, s, v), inv, q);
+  const float q2 = __builtin_fmaf(__builtin_fmaf(-q1, s, v), inv, q1);
+  const float r = __builtin_rintf((__builtin_isfinite(q) ? q2 : q) + zp);
+  return fminf(fmaxf(r, -128.f), 127.f);
+}
+__device__ __forceinline__ float2_t q8_exact2_zp(float2_t v, float s, float inv, float lim, float zp) {
+  v = float2_t{__builtin_amdgcn_fmed3f(v.x, -lim, lim), __builtin_amdgcn_fmed3f(v.y, -lim, lim)};
+  const float2_t sv = (float2_t)(s), iv = (float2_t)(inv);
+  const float2_t q = v * iv;
+  const float2_t q1 = __builtin_elementwise_fma(__builtin_elementwise_fma(-q, sv, v), iv, q);
+  const float2_t q2 = __builtin_elementwise_fma(__builtin_elementwise_fma(-q1, sv, v), iv, q1) + (float2_t)(zp);
+  return float2_t{__builtin_amdgcn_fmed3f(__builtin_rintf(q2.x), -128.f, 127.f),
+                  __builtin_amdgcn_fmed3f(__builtin_rintf(q2.y), -128.f, 127.f)};
+}
 // round_half_even(v * fl(1/s)), NOT clamped: the quotient by one reciprocal multiply (<= 1.5 ulp from
 // v / s, so a code differs from the exact quotient's only within ~1e-7 of a rounding midpoint); the
 // clamp to [-128, 127] is q8_pack4's saturating conversion.  For the GELU epilogues only: the GELU in
@@ -193,6 +214,11 @@ __device__ __forceinline__ float2_t q8_exact2(float2_t v, float s, float inv, fl
 // q8_exact2 buys nothing there; 3 VALU per pair instead of 11.
 __device__ __forceinline__ float2_t q8_recip2(float2_t v, float inv) {
   const float2_t q = v * (float2_t)(inv);
+  return float2_t{__builtin_rintf(q.x), __builtin_rintf(q.y)};
+}
+// the same under a zero point: round_half_even(fma(v, fl(1/s), zp)) -- one rounding of quotient + zp
+__device__ __forceinline__ float2_t q8_recip2(float2_t v, float inv, float zp) {
+  const float2_t q = __builtin_elementwise_fma(v, (float2_t)(inv), (float2_t)(zp));
   return float2_t{__builtin_rintf(q.x), __builtin_rintf(q.y)};
 }
 // four codes (integer floats) -> their int8 bytes in one dword: v_cvt_pk_u8_f32 of code + 128 per

@@ -18,6 +18,11 @@
 //   Q8_RES  out = q(R * res_scale + fq(y, mid_scale), out_scale)   (proj -> qact3 -> +x -> qact2)
 //           (mid_scale <= 0: no intermediate quantiser); R int8 codes, may alias C.
 //
+// Activations with zero points (samq_i8_gemm_zp, samq_w8a8_conv_gemm_zp; W8, the three quantising
+// epilogues): the ring kernels instantiated on I8EpiZp (gemm_i8_epilogue.h) -- an int32 col_offset[n]
+// = -zp_a * sum_k W[n, k] joins the sum before the scaling, the quantisers and the residual carry
+// their zero points.  The symmetric instantiations are untouched.
+//
 // The kernels: gemm_i8_ring.h (2- / 3-slot LDS ring, every weight format), gemm_i8_pp.h (W4
 // ping-pong), gemm_i8_epilogue.h (their shared epilogue).  Here: the W8 repack, the launchers, the
 // tile-config table and the C entry points.
@@ -48,13 +53,28 @@ __global__ void w8_repack_kernel(const int8_t* __restrict__ w, int8_t* __restric
 struct I8Args {
   const int8_t* A; int64_t lda; const char* Wp; const float* wscale; const uint32_t* qzeros;
   const float* bias; void* C; int64_t ldc; int M, N, K; I8Epi ep; I8Gather ga;
+  // the _zp entries only (launch_i8<..., ZP = true>): the I8EpiZp fields beyond ep
+  const int* col_offset = nullptr; float mid_zp = 0.f, res_zp = 0.f, out_zp = 0.f; const int8_t* pad16 = nullptr;
 };
 
-template <int BM, int BN, int WMW, int WNW, int EPI, int BF, int ST, int AG = AG_ROWS, bool GRP = false>
+template <int BM, int BN, int WMW, int WNW, int EPI, int BF, int ST, int AG = AG_ROWS, bool GRP = false, bool ZP = false>
 static int launch_i8(const I8Args& a, hipStream_t st) {
   const int nwg = ((a.M + BM - 1) / BM) * (a.N / BN);
-  hipLaunchKernelGGL((i8_gemm_kernel<BM, BN, WMW, WNW, EPI, BF, ST, AG, GRP>), dim3(nwg), dim3(64 * WMW * WNW), 0, st,
-                     a.A, a.lda, a.Wp, a.wscale, a.qzeros, a.bias, a.C, a.ldc, a.M, a.N, a.K, a.ep, a.ga);
+  if constexpr (ZP) {
+    I8EpiZp ez;
+    static_cast<I8Epi&>(ez) = a.ep;
+    ez.col_offset = a.col_offset;
+    ez.mid_zp = a.mid_zp;
+    ez.res_zp = a.res_zp;
+    ez.out_zp = a.out_zp;
+    ez.pad16 = a.pad16;
+    hipLaunchKernelGGL((i8_gemm_kernel<BM, BN, WMW, WNW, EPI, BF, ST, AG, GRP, I8EpiZp>), dim3(nwg),
+                       dim3(64 * WMW * WNW), 0, st, a.A, a.lda, a.Wp, a.wscale, a.qzeros, a.bias, a.C, a.ldc, a.M, a.N,
+                       a.K, ez, a.ga);
+  } else {
+    hipLaunchKernelGGL((i8_gemm_kernel<BM, BN, WMW, WNW, EPI, BF, ST, AG, GRP>), dim3(nwg), dim3(64 * WMW * WNW), 0, st,
+                       a.A, a.lda, a.Wp, a.wscale, a.qzeros, a.bias, a.C, a.ldc, a.M, a.N, a.K, a.ep, a.ga);
+  }
   SAMQ_LAUNCH_CHECK("i8_gemm launch");
   return SAMQ_OK;
 }
@@ -89,6 +109,10 @@ struct I8Ring {
   static int launch_grouped(const I8Args& a, hipStream_t st) {
     return launch_i8<BM, BN, WMW, WNW, EPI, BF_W4, ST4, AG_ROWS, true>(a, st);
   }
+  template <int EPI>
+  static int launch_zp(const I8Args& a, hipStream_t st) {   // W8, activations with zero points
+    return launch_i8<BM, BN, WMW, WNW, EPI, BF_W8, ST8, AG_ROWS, false, true>(a, st);
+  }
 };
 template <int BM, int BN, int WMW, int WNW, int ST>
 using I8RingG = I8Ring<BM, BN, WMW, WNW, ST, ST, true>;
@@ -106,6 +130,10 @@ struct I8Pp {
     else if (FLAGS == I8PP_ROW_SUMS && a.ep.rs_in) return launch_i8_pp2<EPI, I8PP_ROW_SUMS | I8PP_RS_IN>(a, st);
     else return launch_i8_pp2<EPI, FLAGS>(a, st);
   }
+  template <int EPI>
+  static int launch_zp(const I8Args&, hipStream_t) {
+    return fail(SAMQ_ERR_INVALID, "i8_gemm_zp: cfg " + std::to_string(ID) + " is the W4 ping-pong kernel");
+  }
 };
 
 struct I8NoTile {   // an id the table does not have
@@ -113,6 +141,8 @@ struct I8NoTile {   // an id the table does not have
   static constexpr bool GROUPED = false;
   template <int EPI, int BF>
   static int launch(const I8Args&, hipStream_t) { return fail(SAMQ_ERR_INVALID, "i8_gemm: unknown tile config"); }
+  template <int EPI>
+  static int launch_zp(const I8Args&, hipStream_t) { return fail(SAMQ_ERR_INVALID, "i8_gemm_zp: unknown tile config"); }
 };
 
 // ---- the config table: f(row) for the row of tile config id cfg (f(I8NoTile) for any other id).
@@ -153,6 +183,12 @@ static int i8_cfg_bn(int cfg) { return with_i8_cfg(cfg, [](auto row) { return de
 template <int EPI, int BF>
 static int launch_i8_cfg(const I8Args& a, int cfg, hipStream_t st) {
   return with_i8_cfg(cfg, [&](auto row) { return decltype(row)::template launch<EPI, BF>(a, st); });
+}
+
+// W8 on activations with zero points (samq_i8_gemm_zp)
+template <int EPI>
+static int launch_i8_cfg_zp(const I8Args& a, int cfg, hipStream_t st) {
+  return with_i8_cfg(cfg, [&](auto row) { return decltype(row)::template launch_zp<EPI>(a, st); });
 }
 
 // grouped W4 (ep.kpg K tiles per group)
@@ -300,6 +336,94 @@ extern "C" int samq_w8a8_conv_gemm(const int8_t* x, int mode, int B, int Cin, in
                             : launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8, BF_W8, 3, AG_3X3>(a, stream);
   return mode == AG_PATCH ? launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8_RES, BF_W8, 3, AG_PATCH>(a, stream)
                           : launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8_RES, BF_W8, 3, AG_3X3>(a, stream);
+}
+
+// The zero-point arguments shared by samq_i8_gemm_zp and samq_w8a8_conv_gemm_zp
+static int i8_zp_args(I8Args& a, const int32_t* col_offset, int mid_zp, int res_zp, int out_zp, const char* who) {
+  auto ok = [](int z) { return z >= -128 && z <= 127; };
+  SAMQ_REQUIRE(ok(mid_zp) && ok(res_zp) && ok(out_zp), SAMQ_ERR_INVALID,
+               std::string(who) + ": zero points must be in [-128, 127]");
+  SAMQ_REQUIRE(((uintptr_t)col_offset & 3) == 0, SAMQ_ERR_INVALID, std::string(who) + ": col_offset must be 4-byte aligned");
+  a.col_offset = col_offset;
+  a.mid_zp = (float)mid_zp;
+  a.res_zp = (float)res_zp;
+  a.out_zp = (float)out_zp;
+  return SAMQ_OK;
+}
+
+extern "C" int samq_i8_gemm_zp(const int8_t* A, int64_t lda, const int8_t* wpacked, const float* wscale,
+                               const float* bias, void* C, int64_t ldc, const int8_t* R, int64_t ldr, int M, int N,
+                               int K, int epilogue, float a_scale, float mid_scale, float res_scale, float out_scale,
+                               int cfg, const int32_t* col_offset, int mid_zp, int res_zp, int out_zp, int rmod,
+                               hipStream_t stream) {
+  if (M == 0) return SAMQ_OK;   // empty batch: no work, data pointers may be null
+  SAMQ_REQUIRE(epilogue == SAMQ_EPI_Q8 || epilogue == SAMQ_EPI_Q8_GELU || epilogue == SAMQ_EPI_Q8_RES,
+               SAMQ_ERR_UNSUPPORTED, "i8_gemm_zp: epilogue must be Q8, Q8_GELU or Q8_RES");
+  SAMQ_REQUIRE(A && wpacked && wscale && C, SAMQ_ERR_INVALID, "i8_gemm_zp: null pointer");
+  SAMQ_REQUIRE(M >= 0 && N > 0 && K > 0 && K % 128 == 0, SAMQ_ERR_INVALID, "i8_gemm_zp: K must be a multiple of 128");
+  SAMQ_REQUIRE(N % 64 == 0, SAMQ_ERR_INVALID, "i8_gemm_zp: N must be a multiple of 64");
+  SAMQ_REQUIRE(lda >= K && lda % 16 == 0 && ((uintptr_t)A & 15) == 0, SAMQ_ERR_INVALID,
+               "i8_gemm_zp: A must be 16-byte aligned with lda >= K, lda % 16 == 0");
+  SAMQ_REQUIRE(ldc >= N && ldc % 16 == 0 && ((uintptr_t)C & 15) == 0, SAMQ_ERR_INVALID,
+               "i8_gemm_zp: C must be 16-byte aligned rows, ldc >= N");
+  SAMQ_REQUIRE(out_scale > 0.f, SAMQ_ERR_INVALID, "i8_gemm_zp: needs out_scale > 0");
+  SAMQ_REQUIRE(epilogue != SAMQ_EPI_Q8_RES || (R && ldr >= N && ldr % 16 == 0 && ((uintptr_t)R & 15) == 0),
+               SAMQ_ERR_INVALID, "i8_gemm_zp: Q8_RES needs a 16-byte aligned residual R with ldr >= N, ldr % 16 == 0");
+  SAMQ_REQUIRE(rmod >= 0, SAMQ_ERR_INVALID, "i8_gemm_zp: rmod must be >= 0");
+  if (cfg <= 0) cfg = i8_pick_cfg(M, N, BF_W8);
+  SAMQ_REQUIRE(i8_cfg_bn(cfg) > 0, SAMQ_ERR_INVALID, "i8_gemm_zp: unknown tile config");
+  SAMQ_REQUIRE(N % i8_cfg_bn(cfg) == 0, SAMQ_ERR_INVALID, "i8_gemm_zp: N not divisible by tile");
+  I8Args a{A, lda, (const char*)wpacked, wscale, nullptr, bias, C, ldc, M, N, K,
+           I8Epi{a_scale, mid_scale, res_scale, out_scale, R, ldr, rmod}, I8Gather{0, 0, 0}};
+  if (const int e = i8_zp_args(a, col_offset, mid_zp, res_zp, out_zp, "i8_gemm_zp")) return e;
+  switch (epilogue) {
+    case SAMQ_EPI_Q8: return launch_i8_cfg_zp<SAMQ_EPI_Q8>(a, cfg, stream);
+    case SAMQ_EPI_Q8_GELU: return launch_i8_cfg_zp<SAMQ_EPI_Q8_GELU>(a, cfg, stream);
+    default: return launch_i8_cfg_zp<SAMQ_EPI_Q8_RES>(a, cfg, stream);
+  }
+}
+
+extern "C" int samq_w8a8_conv_gemm_zp(const int8_t* x, int mode, int B, int Cin, int side, const int8_t* wpacked,
+                                      const float* wscale, const float* bias, void* C, const int8_t* R, int rmod,
+                                      int N, int epilogue, float a_scale, float mid_scale, float res_scale,
+                                      float out_scale, const int32_t* col_offset, int mid_zp, int res_zp, int out_zp,
+                                      const int8_t* pad16, hipStream_t stream) {
+  if (B == 0) return SAMQ_OK;   // empty batch: no work, data pointers may be null
+  SAMQ_REQUIRE(x && wpacked && wscale && C, SAMQ_ERR_INVALID, "w8a8_conv_gemm_zp: null pointer");
+  SAMQ_REQUIRE(mode == AG_PATCH || mode == AG_3X3, SAMQ_ERR_INVALID,
+               "w8a8_conv_gemm_zp: mode must be 1 (patch) or 2 (3x3)");
+  SAMQ_REQUIRE(epilogue == SAMQ_EPI_Q8 || epilogue == SAMQ_EPI_Q8_RES, SAMQ_ERR_UNSUPPORTED,
+               "w8a8_conv_gemm_zp: epilogue must be Q8 or Q8_RES");
+  SAMQ_REQUIRE(B > 0 && Cin > 0 && side > 0 && N > 0 && N % 64 == 0, SAMQ_ERR_INVALID, "w8a8_conv_gemm_zp: bad shape");
+  SAMQ_REQUIRE(out_scale > 0.f, SAMQ_ERR_INVALID, "w8a8_conv_gemm_zp: needs out_scale > 0");
+  SAMQ_REQUIRE(epilogue != SAMQ_EPI_Q8_RES || (R && ((uintptr_t)R & 15) == 0), SAMQ_ERR_INVALID,
+               "w8a8_conv_gemm_zp: Q8_RES needs a 16-byte aligned residual");
+  SAMQ_REQUIRE(rmod >= 0, SAMQ_ERR_INVALID, "w8a8_conv_gemm_zp: rmod must be >= 0");
+  SAMQ_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)C & 15) == 0, SAMQ_ERR_INVALID,
+               "w8a8_conv_gemm_zp: operands must be 16-byte aligned");
+  SAMQ_REQUIRE(mode != AG_3X3 || (pad16 && ((uintptr_t)pad16 & 15) == 0), SAMQ_ERR_INVALID,
+               "w8a8_conv_gemm_zp: 3x3 mode needs pad16, 16 bytes of the input's zero-point code, 16-byte aligned");
+  int G, K;
+  if (mode == AG_PATCH) {
+    SAMQ_REQUIRE(side % 16 == 0 && (Cin * 256) % 128 == 0, SAMQ_ERR_UNSUPPORTED,
+                 "w8a8_conv_gemm_zp: patch mode is the 16x16 / stride 16 PatchEmbed");
+    G = side / 16;
+    K = Cin * 256;
+  } else {
+    SAMQ_REQUIRE(Cin % 128 == 0, SAMQ_ERR_UNSUPPORTED, "w8a8_conv_gemm_zp: 3x3 mode needs Cin % 128 == 0");
+    G = side;
+    K = 9 * Cin;
+  }
+  const int M = B * G * G;
+  I8Args a{x, K, (const char*)wpacked, wscale, nullptr, bias, C, N, M, N, K,
+           I8Epi{a_scale, mid_scale, res_scale, out_scale, R, N, rmod}, I8Gather{side, G, Cin}};
+  if (const int e = i8_zp_args(a, col_offset, mid_zp, res_zp, out_zp, "w8a8_conv_gemm_zp")) return e;
+  a.pad16 = pad16;
+  if (epilogue == SAMQ_EPI_Q8)
+    return mode == AG_PATCH ? launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8, BF_W8, 3, AG_PATCH, false, true>(a, stream)
+                            : launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8, BF_W8, 3, AG_3X3, false, true>(a, stream);
+  return mode == AG_PATCH ? launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8_RES, BF_W8, 3, AG_PATCH, false, true>(a, stream)
+                          : launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8_RES, BF_W8, 3, AG_3X3, false, true>(a, stream);
 }
 
 extern "C" int samq_w8a8_gemm(const int8_t* A, int64_t lda, const int8_t* wpacked, const float* wscale,

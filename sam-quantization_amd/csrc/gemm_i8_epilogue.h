@@ -26,6 +26,22 @@ struct I8Epi {
   int64_t ldv;
 };
 
+// Activations with zero points (samq_i8_gemm_zp / samq_w8a8_conv_gemm_zp; W8 ring kernels, int8-code
+// epilogues): the kernels instantiated on I8EpiZp take
+//   col_offset  int32 [N] (null = 0), added to every row's int32 sum at the head of the epilogue: the
+//               INPUT's zero point, -zp_a * sum_k W[n, k] (sum_k (a - zp_a) w = sum a w - zp_a sum w,
+//               exact in int32; folded into the float bias it would nearly cancel against the sum);
+//   mid_zp / res_zp / out_zp  the zero points of the mid quantiser, the residual codes and the output
+//               quantiser (integers in [-128, 127] as floats; q8_exact2_zp, common.h);
+//   pad16       AG_3X3: 16 bytes of the input's zero-point code, the gather's source outside the map
+//               (a padded 0.0 is the code zp_a), so col_offset holds for border pixels too.
+// The symmetric kernels keep I8Epi: their arguments and code are untouched.
+struct I8EpiZp : I8Epi {
+  const int* col_offset;
+  float mid_zp, res_zp, out_zp;
+  const int8_t* pad16;
+};
+
 // The W4 unpack of both kernels: four nibbles q (one per byte) minus the zero point zpx (zp in
 // every byte) as int8 -- bytes(q) | 0x80 minus zp per byte never borrows, ^0x80 -> int8
 __device__ __forceinline__ int w4_to_i8(uint32_t nib, uint32_t zpx) {
@@ -45,17 +61,29 @@ __device__ __forceinline__ int w4_to_i8(uint32_t nib, uint32_t zpx) {
 // where not null, receives slice i + 1's before this slice's stores; scb = the factors and biases
 // of this lane's columns, loaded once per tile by i8_epilogue (reloaded per slice, their waits
 // would drain the residual loads).
-template <int TM, int TN, int WN, int EPI, bool ZPS = false, typename AccV = int16_t_v>
+template <int TM, int TN, int WN, int EPI, bool ZPS = false, typename AccV = int16_t_v, typename EpiArgs = I8Epi>
 __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][TN], const int (&col)[TN],
                                                   const float* __restrict__ wscale, const float* __restrict__ bias,
-                                                  const I8Epi& ep_args, float* ep, void* __restrict__ Cout,
+                                                  const EpiArgs& ep_args, float* ep, void* __restrict__ Cout,
                                                   int64_t ldc, int M, int row_base, int col_base, int lane,
                                                   const int* ssum = nullptr, const int* zpv = nullptr,
                                                   const float4_t* xcur = nullptr, float4_t* xnext = nullptr,
                                                   const float* scb = nullptr) {
   constexpr bool RESB = EPI == SAMQ_EPI_RESADD_F32;
+  constexpr bool ZP = std::is_same<EpiArgs, I8EpiZp>::value;   // activations with zero points
+  static_assert(!ZP || (!ZPS && (EPI == SAMQ_EPI_Q8 || EPI == SAMQ_EPI_Q8_GELU || EPI == SAMQ_EPI_Q8_RES)),
+                "zero points: W8 weights, int8-code epilogues");
   const int hsel = lane >> 5;
   float csc[TN], cb[TN];
+  int coff[ZP ? TN : 1];
+  float zp_mid = 0.f, zp_res = 0.f, zp_out = 0.f;
+  if constexpr (ZP) {
+#pragma unroll
+    for (int t = 0; t < TN; ++t) coff[t] = ep_args.col_offset ? ep_args.col_offset[col[t]] : 0;
+    zp_mid = ep_args.mid_zp;
+    zp_res = ep_args.res_zp;
+    zp_out = ep_args.out_zp;
+  }
 #pragma unroll
   for (int t = 0; t < TN; ++t) {
     if constexpr (RESB) {
@@ -69,7 +97,8 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
   constexpr bool GELU = EPI == SAMQ_EPI_BIAS_GELU || EPI == SAMQ_EPI_Q8_GELU;
   const float inv_out = ep_args.out_scale > 0.f ? 1.0f / ep_args.out_scale : 0.f;   // q8_exact (common.h)
   const float inv_mid = ep_args.mid_scale > 0.f ? 1.0f / ep_args.mid_scale : 0.f;
-  const float lim_out = 130.0f * ep_args.out_scale, lim_mid = 130.0f * ep_args.mid_scale;   // q8_exact2 clamps
+  // q8_exact2 clamps (260: a quotient of -255.5 still rounds into the code range under a zero point of 127)
+  const float lim_out = (ZP ? 260.0f : 130.0f) * ep_args.out_scale, lim_mid = (ZP ? 260.0f : 130.0f) * ep_args.mid_scale;
   // staging swizzle: the readers below take 64 B (int8 path: 16 columns, 4 ds_read_b128) or 32 B
   // (f16 path: 8 columns, 2 reads) of one row per lane, and a ds_read_b128 lane group spans 4 rows
   // whose k-th 16-byte chunks sat on the same banks (PMC: 3.9 M conflict cycles per W4A8 lin1
@@ -96,6 +125,10 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
           if constexpr (ZPS) {   // v_mad_i32_i24 (zpv = -zp; |S| <= 128 K < 2^23: K < 65536 checked at launch)
             a0 += __mul24(zpv[t], ssum[i * 32 + rl]);
             a1 += __mul24(zpv[t], ssum[i * 32 + rl + 1]);
+          }
+          if constexpr (ZP) {   // the input's zero point: -zp_a * sum_k W[n, k], exact in int32
+            a0 += coff[t];
+            a1 += coff[t];
           }
           y[((r - r0) / 2) * TN + t] = __builtin_elementwise_fma((float2_t){(float)a0, (float)a1}, (float2_t)(csc[t]),
                                                                  (float2_t)(cb[t]));
@@ -182,6 +215,24 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
 #pragma unroll
               for (int b = 0; b < 4; b += 2) {
                 float2_t x = {v[4 * w + b], v[4 * w + b + 1]};
+                if constexpr (ZP) {
+                  if (EPI == SAMQ_EPI_Q8_RES) {
+                    if (ep_args.mid_scale > 0.f)
+                      x = (q8_exact2_zp(x, ep_args.mid_scale, inv_mid, lim_mid, zp_mid) - (float2_t)(zp_mid)) *
+                          ep_args.mid_scale;
+                    const float2_t rv = (float2_t{(float)(int8_t)((res[w] >> (8 * b)) & 0xFFu),
+                                                  (float)(int8_t)((res[w] >> (8 * b + 8)) & 0xFFu)} -
+                                         (float2_t)(zp_res)) * ep_args.res_scale;   // code - zp: exact
+                    x = rv + x;
+                  }
+                  // Q8_GELU: the reciprocal-multiply quotient as in the symmetric kernel (q8_recip2), the
+                  // zero point added before the rounding; q8_pack4 saturates
+                  const float2_t q = EPI == SAMQ_EPI_Q8_GELU ? q8_recip2(x, inv_out, zp_out)
+                                                             : q8_exact2_zp(x, ep_args.out_scale, inv_out, lim_out, zp_out);
+                  cq[b] = q.x;
+                  cq[b + 1] = q.y;
+                  continue;
+                }
                 if (EPI == SAMQ_EPI_Q8_RES) {
                   if (ep_args.mid_scale > 0.f) x = q8_exact2(x, ep_args.mid_scale, inv_mid, lim_mid) * ep_args.mid_scale;
                   const float2_t rv = float2_t{(float)(int8_t)((res[w] >> (8 * b)) & 0xFFu),
@@ -200,7 +251,7 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
               o[w] = q8_pack4(cq[0], cq[1], cq[2], cq[3]);
             }
             *(u32x4*)((int8_t*)Cout + (int64_t)row * ldc + col_base + 16 * c16) = o;
-            if constexpr (EPI == SAMQ_EPI_Q8) {
+            if constexpr (EPI == SAMQ_EPI_Q8 && !ZP) {   // (no fp16 V copy under zero points)
               // v16_col0 is a multiple of 64 (samq_w8a8_gemm_v16): a wave of at most 64 columns, at a
               // multiple of WN, lies wholly on one side of it
               static_assert(WN <= 64 && 64 % WN == 0, "v16 store: a wave's columns must not straddle v16_col0");
@@ -235,10 +286,10 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
 }
 
 // All TM slices of the wave's tile
-template <int TM, int TN, int WN, int EPI, bool ZPS = false, typename AccV = int16_t_v>
+template <int TM, int TN, int WN, int EPI, bool ZPS = false, typename AccV = int16_t_v, typename EpiArgs = I8Epi>
 __device__ __forceinline__ void i8_epilogue(const AccV (&acc)[TM][TN], const int (&col)[TN],
                                             const float* __restrict__ wscale, const float* __restrict__ bias,
-                                            const I8Epi& ep_args, float* ep, void* __restrict__ Cout, int64_t ldc,
+                                            const EpiArgs& ep_args, float* ep, void* __restrict__ Cout, int64_t ldc,
                                             int M, int row_base, int col_base, int lane,
                                             const int* ssum = nullptr, const int* zpv = nullptr) {
   if constexpr (EPI == SAMQ_EPI_RESADD_F32) {

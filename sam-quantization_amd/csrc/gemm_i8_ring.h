@@ -36,12 +36,18 @@ __device__ __forceinline__ void vm_wait_i8() {
 // the group is applied per byte in the unpack as for per-channel weights.  wscale is the f32
 // [G, N] scale table; the next group's zero / scale words are loaded one K tile ahead, before the
 // tile's LDS-DMA pieces (so the ring's counted vmcnt covers them).
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int BFMT, int STAGES, int AG = AG_ROWS, bool GRP = false>
+// EpiArgs = I8EpiZp (W8 only): activations with zero points -- the epilogue adds col_offset and
+// carries the quantisers' zero points, the 3x3 gather pads with the zero-point code (I8EpiZp,
+// gemm_i8_epilogue.h); the main loop is the same.
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int BFMT, int STAGES, int AG = AG_ROWS, bool GRP = false,
+          typename EpiArgs = I8Epi>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N)
 void i8_gemm_kernel(const int8_t* __restrict__ A, int64_t lda, const char* __restrict__ Wp,
                     const float* __restrict__ wscale, const uint32_t* __restrict__ qzeros,
                     const float* __restrict__ bias, void* __restrict__ Cout, int64_t ldc,
-                    int M, int N, int K, I8Epi ep_args, I8Gather ga) {
+                    int M, int N, int K, EpiArgs ep_args, I8Gather ga) {
+  constexpr bool ZP = std::is_same<EpiArgs, I8EpiZp>::value;
+  static_assert(!ZP || (BFMT == BF_W8 && !GRP), "zero points: W8 weights");
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int WM = BM / WAVES_M;
   constexpr int WN = BN / WAVES_N;
@@ -110,7 +116,10 @@ void i8_gemm_kernel(const int8_t* __restrict__ A, int64_t lda, const char* __res
     }
     const int tap = k / ga.Cin, c0 = k - tap * ga.Cin;   // AG_3X3: k = (ky * 3 + kx) * Cin + c
     const int sy = gy + tap / 3 - 1, sx = gx + tap % 3 - 1;
-    if (sy < 0 || sy >= ga.G || sx < 0 || sx >= ga.G) return (const char*)g_zero_i8;
+    if (sy < 0 || sy >= ga.G || sx < 0 || sx >= ga.G) {
+      if constexpr (ZP) return (const char*)ep_args.pad16;   // a padded 0.0 is the code zp
+      else return (const char*)g_zero_i8;
+    }
     return (const char*)(A + (((int64_t)b * ga.G + sy) * ga.G + sx) * ga.Cin + c0);
   };
   auto issue = [&](int kt, int slot) {

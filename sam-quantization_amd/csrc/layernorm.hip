@@ -20,7 +20,9 @@ __device__ __forceinline__ float ln_q8(float v, float s) {   // fq_vit uniform.p
 // f32 delta: the same fp32 add as the GEMM's read-modify-write epilogue (bit-identical x).  The ADD
 // variants read AND write the residual through ``xres`` (plain, non-const: the buffer is updated in
 // place); ``xin`` (const restrict) is the input of the ADD == 0 variants only.
-template <int IN, int OUT, int VPT, int RPW, int ADD = 0>
+// ZP (samq_layernorm_q_zp): int8 input (code - zp_in) * in_scale, the subtraction in integers; the
+// output quantiser (out_scale, zp_out) with the fake-quant value (code - zp_out) * out_scale.
+template <int IN, int OUT, int VPT, int RPW, int ADD = 0, bool ZP = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__ xin, void* __restrict__ y,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int64_t rows, int C,
@@ -28,7 +30,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
                                                         float* __restrict__ mean_out,
                                                         const void* __restrict__ delta = nullptr,
                                                         float* xres = nullptr, int* __restrict__ rs_out = nullptr,
-                                                        int* __restrict__ rs_zero = nullptr) {
+                                                        int* __restrict__ rs_zero = nullptr, int zp_in = 0,
+                                                        float zp_out = 0.f) {
   static_assert(ADD == 0 || IN == LN_F32, "residual add: f32 rows");
   const int lane = threadIdx.x & 63;
   const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
@@ -49,7 +52,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
         } else if (IN == LN_I8) {
           const uint32_t w = ((const uint32_t*)xin)[row * nvec + j];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[r][i][e] = (float)(int8_t)((w >> (8 * e)) & 0xFFu) * in_scale;
+          for (int e = 0; e < 4; ++e) {
+            if constexpr (ZP) v[r][i][e] = (float)((int)(int8_t)((w >> (8 * e)) & 0xFFu) - zp_in) * in_scale;
+            else v[r][i][e] = (float)(int8_t)((w >> (8 * e)) & 0xFFu) * in_scale;
+          }
         } else {
           v[r][i] = ADD != 0 ? ((const float4_t*)xres)[row * nvec + j] : ((const float4_t*)xin)[row * nvec + j];
           if constexpr (ADD == 1) {
@@ -126,12 +132,21 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
           ((float4_t*)y)[row * nvec + j] = o;
         } else if (OUT == LN_FQ32) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = ln_q8(o[e], out_scale) * out_scale;
+          for (int e = 0; e < 4; ++e) {
+            if constexpr (ZP) o[e] = (q8_exact_zp(o[e], out_scale, 1.0f / out_scale, zp_out) - zp_out) * out_scale;
+            else o[e] = ln_q8(o[e], out_scale) * out_scale;
+          }
           ((float4_t*)y)[row * nvec + j] = o;
         } else if (OUT == LN_I8) {
-          const float inv = 1.0f / out_scale, lim = 130.0f * out_scale;   // (loop-invariant: hoisted)
-          const float2_t c01 = q8_exact2(float2_t{o[0], o[1]}, out_scale, inv, lim);
-          const float2_t c23 = q8_exact2(float2_t{o[2], o[3]}, out_scale, inv, lim);
+          const float inv = 1.0f / out_scale, lim = (ZP ? 260.0f : 130.0f) * out_scale;   // (loop-invariant: hoisted)
+          float2_t c01, c23;
+          if constexpr (ZP) {
+            c01 = q8_exact2_zp(float2_t{o[0], o[1]}, out_scale, inv, lim, zp_out);
+            c23 = q8_exact2_zp(float2_t{o[2], o[3]}, out_scale, inv, lim, zp_out);
+          } else {
+            c01 = q8_exact2(float2_t{o[0], o[1]}, out_scale, inv, lim);
+            c23 = q8_exact2(float2_t{o[2], o[3]}, out_scale, inv, lim);
+          }
           const uint32_t wq = q8_pack4(c01.x, c01.y, c23.x, c23.y);
           ((uint32_t*)y)[row * nvec + j] = wq;
           if (rs_out) rsi = __builtin_amdgcn_sdot4((int)wq, 0x01010101, rsi, false);
@@ -161,7 +176,8 @@ static int ln_rpw(int flags) {
 
 static int ln_launch(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C, float eps,
                      int in, int out, float in_scale, float out_scale, int rpw, hipStream_t stream,
-                     float* mean_out = nullptr, int* rs_out = nullptr, int* rs_zero = nullptr) {
+                     float* mean_out = nullptr, int* rs_out = nullptr, int* rs_zero = nullptr, bool zp = false,
+                     int zp_in = 0, int zp_out = 0) {
   if (rows == 0) return SAMQ_OK;   // empty batch: no work, data pointers may be null
   SAMQ_REQUIRE(x && y && gamma && beta, SAMQ_ERR_INVALID, "layernorm: null pointer");
   SAMQ_REQUIRE(C > 0 && C % 4 == 0 && C <= 4096, SAMQ_ERR_INVALID, "layernorm: C must be a multiple of 4, <= 4096");
@@ -170,8 +186,11 @@ static int ln_launch(const void* x, void* y, const float* gamma, const float* be
   const int vpt = (C / 4 + 63) / 64;
   if (vpt > 5) rpw = 1;
   const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
+  // zero points (samq_layernorm_q_zp): the ZP kernels; int8 on at least one side
+#define LN_Z(I, O, V, R) hipLaunchKernelGGL((layernorm_kernel<I, O, V, R, 0, true>), grid, dim3(256), 0, stream, x, y, gamma, beta, rows, C, eps, in_scale, out_scale, mean_out, nullptr, nullptr, rs_out, rs_zero, zp_in, (float)zp_out)
 #define LN_R(I, O, V) \
   do { \
+    if (zp) { if (rpw == 1) LN_Z(I, O, V, 1); else if (rpw == 2) LN_Z(I, O, V, 2); else LN_Z(I, O, V, 4); break; } \
     if (rpw == 1) hipLaunchKernelGGL((layernorm_kernel<I, O, V, 1>), grid, dim3(256), 0, stream, x, y, gamma, beta, rows, C, eps, in_scale, out_scale, mean_out, nullptr, nullptr, rs_out, rs_zero); \
     else if (rpw == 2) hipLaunchKernelGGL((layernorm_kernel<I, O, V, 2>), grid, dim3(256), 0, stream, x, y, gamma, beta, rows, C, eps, in_scale, out_scale, mean_out, nullptr, nullptr, rs_out, rs_zero); \
     else hipLaunchKernelGGL((layernorm_kernel<I, O, V, 4>), grid, dim3(256), 0, stream, x, y, gamma, beta, rows, C, eps, in_scale, out_scale, mean_out, nullptr, nullptr, rs_out, rs_zero); \
@@ -193,6 +212,7 @@ static int ln_launch(const void* x, void* y, const float* gamma, const float* be
 #undef LN_O
 #undef LN_V
 #undef LN_R
+#undef LN_Z
   SAMQ_LAUNCH_CHECK("layernorm launch");
   return SAMQ_OK;
 }
@@ -247,6 +267,20 @@ extern "C" int samq_layernorm_q(const void* x, void* y, const float* gamma, cons
   const int out = (flags & SAMQ_LN_OUT_I8) ? ((flags & SAMQ_LN_OUT_F32) ? LN_FQ32 : LN_I8)
                                            : ((flags & SAMQ_LN_OUT_F32) ? LN_F32 : LN_F16);
   return ln_launch(x, y, gamma, beta, rows, C, eps, in, out, in_scale, out_scale, ln_rpw(flags), stream);
+}
+
+extern "C" int samq_layernorm_q_zp(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C,
+                                   float eps, int flags, float in_scale, float out_scale, int zp_in, int zp_out,
+                                   hipStream_t stream) {
+  SAMQ_REQUIRE(!(flags & SAMQ_LN_IN_I8) || in_scale > 0.f, SAMQ_ERR_INVALID, "layernorm_q_zp: in_scale must be > 0");
+  SAMQ_REQUIRE(!(flags & SAMQ_LN_OUT_I8) || out_scale > 0.f, SAMQ_ERR_INVALID, "layernorm_q_zp: out_scale must be > 0");
+  SAMQ_REQUIRE(zp_in >= -128 && zp_in <= 127 && zp_out >= -128 && zp_out <= 127, SAMQ_ERR_INVALID,
+               "layernorm_q_zp: zero points must be in [-128, 127]");
+  const int in = (flags & SAMQ_LN_IN_I8) ? LN_I8 : ((flags & SAMQ_LN_IN_F16) ? LN_F16 : LN_F32);
+  const int out = (flags & SAMQ_LN_OUT_I8) ? ((flags & SAMQ_LN_OUT_F32) ? LN_FQ32 : LN_I8)
+                                           : ((flags & SAMQ_LN_OUT_F32) ? LN_F32 : LN_F16);
+  return ln_launch(x, y, gamma, beta, rows, C, eps, in, out, in_scale, out_scale, ln_rpw(flags), stream, nullptr,
+                   nullptr, nullptr, true, zp_in, zp_out);
 }
 
 // LN-q with the output rows' code sums (round 6): rowsum[r] = sum_c y[r, c] (int8 codes, SAMQ_LN_OUT_I8

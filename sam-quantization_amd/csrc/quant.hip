@@ -8,9 +8,11 @@
 
 namespace samq {
 
-template <bool IN_F16, bool OUT_FQ>
+// ZP: the quantiser (s, zp) of samq_quantize_zp -- the zero point added to the exact quotient before
+// the rounding (q8_exact_zp), the fake-quant value (code - zp) * s
+template <bool IN_F16, bool OUT_FQ, bool ZP = false>
 __global__ __launch_bounds__(256) void quantize_kernel(const void* __restrict__ x, void* __restrict__ y, int64_t n,
-                                                       float s) {
+                                                       float s, float zp = 0.f) {
   const float inv = 1.0f / s;   // q8_exact (common.h): multiply + two Markstein corrections
   const int64_t n4 = n / 4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -35,7 +37,14 @@ __global__ __launch_bounds__(256) void quantize_kernel(const void* __restrict__ 
     }
     float q[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) q[e] = q8_exact(v[e], s, inv);
+    for (int e = 0; e < 4; ++e) {
+      if constexpr (ZP) q[e] = q8_exact_zp(v[e], s, inv, zp);
+      else q[e] = q8_exact(v[e], s, inv);
+    }
+    if constexpr (ZP && OUT_FQ) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) q[e] -= zp;
+    }
     if (OUT_FQ) {
       if (cnt == 4) ((float4_t*)y)[i] = float4_t{q[0] * s, q[1] * s, q[2] * s, q[3] * s};
       else ((float*)y)[base] = q[0] * s;
@@ -74,6 +83,30 @@ extern "C" int samq_quantize(const void* x, void* y, int64_t n, float scale, int
     else hipLaunchKernelGGL((quantize_kernel<false, false>), dim3(blocks), dim3(256), 0, stream, x, y, n, scale);
   }
   SAMQ_LAUNCH_CHECK("quantize launch");
+  return SAMQ_OK;
+}
+
+extern "C" int samq_quantize_zp(const void* x, void* y, int64_t n, float scale, int zp, int flags,
+                                hipStream_t stream) {
+  if (n == 0) return SAMQ_OK;   // empty batch: no work, data pointers may be null
+  SAMQ_REQUIRE(x && y, SAMQ_ERR_INVALID, "quantize_zp: null pointer");
+  SAMQ_REQUIRE(scale > 0.f, SAMQ_ERR_INVALID, "quantize_zp: scale must be > 0");
+  SAMQ_REQUIRE(zp >= -128 && zp <= 127, SAMQ_ERR_INVALID, "quantize_zp: zero point must be in [-128, 127]");
+  SAMQ_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, SAMQ_ERR_INVALID,
+               "quantize_zp: pointers must be 16-byte aligned");
+  if (n <= 0) return SAMQ_OK;
+  const int64_t work = n / 4 + (n & 3);
+  const int blocks = (int)((work + 255) / 256 < 16384 ? (work + 255) / 256 : 16384);
+  const bool f16 = flags & SAMQ_Q_IN_F16, fq = flags & SAMQ_Q_OUT_FQ;
+  const float z = (float)zp;
+  if (f16) {
+    if (fq) hipLaunchKernelGGL((quantize_kernel<true, true, true>), dim3(blocks), dim3(256), 0, stream, x, y, n, scale, z);
+    else hipLaunchKernelGGL((quantize_kernel<true, false, true>), dim3(blocks), dim3(256), 0, stream, x, y, n, scale, z);
+  } else {
+    if (fq) hipLaunchKernelGGL((quantize_kernel<false, true, true>), dim3(blocks), dim3(256), 0, stream, x, y, n, scale, z);
+    else hipLaunchKernelGGL((quantize_kernel<false, false, true>), dim3(blocks), dim3(256), 0, stream, x, y, n, scale, z);
+  }
+  SAMQ_LAUNCH_CHECK("quantize_zp launch");
   return SAMQ_OK;
 }
 

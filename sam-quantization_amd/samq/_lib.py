@@ -115,6 +115,15 @@ SIGNATURES = {
                                    _i32, _vp]),
     "samq_conv1x1_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "samq_conv3x3_nhwc": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    # activation zero points
+    "samq_quantize_zp": (_i32, [_vp, _vp, _i64, _f32, _i32, _i32, _vp]),
+    "samq_layernorm_q_zp": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _f32, _f32, _i32, _i32, _vp]),
+    "samq_i8_gemm_zp": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _f32,
+                               _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "samq_rel_attention_q8_zp": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
+                                        _f32, _f32, _f32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "samq_w8a8_conv_gemm_zp": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                      _f32, _f32, _f32, _f32, _vp, _i32, _i32, _i32, _vp, _vp]),
 }
 
 

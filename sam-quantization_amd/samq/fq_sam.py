@@ -424,6 +424,8 @@ class Sam(_FloatSam):
 
     def _drop_engines(self):
         self.image_encoder._engine = None
+        self.image_encoder._engine_zp = None
+        self.image_encoder._pick_zp = None
         if hasattr(self.mask_decoder, "refresh"):
             self.mask_decoder.refresh()
 

@@ -17,13 +17,19 @@ Mirrors (names, constructor arguments, flags, ``quantizer.scale`` buffers) the r
   ``model_close_calibrate`` / ``model_quant`` / ``model_dequant`` (``models/sam/sam.py:208-235``).
 
 Supported configuration = the one the reference's SAM path uses (``test_quant.py:229-231``):
-``Config(ptf=False, lis=False, quant_method=m)`` with ``BIT_TYPE_A = int8`` and ``m`` any of the
-four observers of ``test_quant.py:34-36`` -- ``minmax``, ``ema``, ``percentile``, ``omse``: int8
-symmetric per-channel weights (always minmax), int8 layer-wise activations, plain LayerNorm /
-softmax.  minmax, ema and percentile give symmetric activations (zero point 0) and run the fused
-engine.  omse searches an asymmetric range, so its zero points are non-zero: it calibrates (on the
-HIP observers) and runs the module graph, and the engine raises ``NotImplementedError`` for it, as
-for every other configuration (``ptf``, ``lis``, other bit types) in quant mode.
+``Config(ptf=False, lis=False, quant_method=m)`` with ``BIT_TYPE_A`` int8 or (the ``Config`` default)
+uint8 and ``m`` any of the four observers of ``test_quant.py:34-36`` -- ``minmax``, ``ema``,
+``percentile``, ``omse``: int8 symmetric per-channel weights (always minmax), 8-bit layer-wise
+activations, plain LayerNorm / softmax.  With int8 activations minmax, ema and percentile give
+symmetric quantisers (zero point 0) and run the symmetric engine, ``enc.engine()``.  omse searches
+an asymmetric range and uint8 observers are asymmetric throughout, so their zero points are
+non-zero: those run the zero-point engine, ``enc.engine(zero_points=True)``, on the ``_zp`` kernels
+-- a quantiser is (scale, zp), ``code = clamp(rint(x / s + zp))``, value ``(code - zp) * s``; uint8
+codes are stored as ``code - 128`` with the zero point ``zp - 128``, so the rounding happens on
+``q + (zp - 128)`` instead of ``q + zp``, which can differ only for quotients within about 2^-17 of
+a tie.  ``enc(img)`` picks the engine by itself; ``enc.engine()`` keeps refusing non-zero zero
+points.  Every other configuration (``ptf``: per-channel activation quantisers, ``lis``, other bit
+widths) raises ``NotImplementedError`` in quant mode.
 
 Every observer has a torch path for CPU tensors (the reference's ops, bit for bit) and a HIP path
 for GPU tensors: ``samq_minmax`` (minmax, ema, omse's statistics), ``samq_order_stats`` (the exact
@@ -791,6 +797,8 @@ class ImageEncoderViT(nn.Module):
         self.global_attn_indexes = tuple(global_attn_indexes)
         self.window_size = window_size
         self._engine = None
+        self._engine_zp = None
+        self._pick_zp = None
 
     # -- calibration switches (fq_vit/models/sam/sam.py:208-235) ------------------------------------
     def _qmods(self):
@@ -800,6 +808,8 @@ class ImageEncoderViT(nn.Module):
         for m in self._qmods():
             m.quant = True
         self._engine = None
+        self._engine_zp = None
+        self._pick_zp = None
 
     def model_dequant(self):
         for m in self._qmods():
@@ -817,6 +827,8 @@ class ImageEncoderViT(nn.Module):
         for m in self._qmods():
             m.calibrate = False
         self._engine = None
+        self._engine_zp = None
+        self._pick_zp = None
 
     @torch.no_grad()
     def calibrate_with(self, images) -> None:
@@ -834,15 +846,37 @@ class ImageEncoderViT(nn.Module):
     def is_quant(self) -> bool:
         return all(m.quant for m in self._qmods() if not isinstance(m, QIntSoftmax))
 
-    def engine(self) -> "W8A8Engine":
+    def engine(self, zero_points: bool = False) -> "W8A8Engine":
+        """The fused HIP engine.  ``zero_points=False``: the symmetric engine (int8 activations, every
+        zero point 0; anything else is refused).  ``zero_points=True``: the zero-point engine (int8 or
+        uint8 activations, any layer-wise zero point), cached separately."""
+        if zero_points:
+            if self._engine_zp is None:
+                self._engine_zp = W8A8Engine(self, zero_points=True)
+            return self._engine_zp
         if self._engine is None:
             self._engine = W8A8Engine(self)
         return self._engine
+
+    def _needs_zero_points(self) -> bool:
+        """Any activation zero point non-zero, or unsigned activation codes."""
+        if not self.cfg.BIT_TYPE_A.signed:
+            return True
+        for m in self.modules():
+            if isinstance(m, QAct):
+                zp = m.quantizer.zero_point
+                if zp is not None and bool((zp != 0).any()):
+                    return True
+        return False
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.is_quant() and not any(m.calibrate for m in self._qmods()):
             if not x.is_cuda:
                 raise RuntimeError("fq_vit ImageEncoderViT: the quantized encoder runs on the GPU (HIP) only")
+            if self._pick_zp is None:   # decided once per calibration (reads the zero points back)
+                self._pick_zp = self._needs_zero_points()
+            if self._pick_zp:
+                return self.engine(zero_points=True).forward(x)
             return self.engine().forward(x)
         return self.module_forward(x)
 
@@ -887,9 +921,10 @@ def act_quantizers(enc: nn.Module) -> dict:
 
 
 @torch.no_grad()
-def set_act_scales(enc: nn.Module, scales: dict) -> None:
+def set_act_scales(enc: nn.Module, scales: dict, zero_points: Optional[dict] = None) -> None:
     """Install calibrated layer-wise activation scales (what a calibrated checkpoint's
-    ``quantizer.scale`` / ``zero_point`` buffers hold) on every named QAct."""
+    ``quantizer.scale`` / ``zero_point`` buffers hold) on every named QAct.  ``zero_points``: name ->
+    zero point (the reference's, in its own bit type's range); None: all zero."""
     qa = act_quantizers(enc)
     missing = set(qa) - set(scales)
     if missing:
@@ -898,7 +933,8 @@ def set_act_scales(enc: nn.Module, scales: dict) -> None:
         q = m.quantizer
         dev = next(enc.parameters()).device
         sc = torch.as_tensor(scales[n], dtype=torch.float32, device=dev).reshape(())
-        for name, val in (("scale", sc), ("zero_point", torch.zeros((), dtype=torch.int64, device=dev))):
+        zp = 0 if zero_points is None else int(zero_points[n])
+        for name, val in (("scale", sc), ("zero_point", torch.full((), zp, dtype=torch.int64, device=dev))):
             if name in q._buffers:
                 q._buffers[name] = val
             else:
@@ -907,6 +943,8 @@ def set_act_scales(enc: nn.Module, scales: dict) -> None:
                 q.register_buffer(name, val)
     if isinstance(enc, ImageEncoderViT):
         enc._engine = None
+        enc._engine_zp = None
+        enc._pick_zp = None
 
 
 @torch.no_grad()
@@ -920,6 +958,8 @@ def calibrate_weights(enc: nn.Module) -> None:
             m.quantizer.update_quantization_params()
     if isinstance(enc, ImageEncoderViT):
         enc._engine = None
+        enc._engine_zp = None
+        enc._pick_zp = None
 
 
 # ----------------------------------------------------------------------------- fused W8A8 engine
@@ -934,8 +974,37 @@ def _s(q: QAct) -> float:
     return float(sc.reshape(-1)[0])
 
 
+def _sz(q: QAct):
+    """(scale, stored zero point) of a layer-wise QAct for the zero-point engine.  The kernels hold
+    int8 codes and a zero point in [-128, 127]; unsigned 8-bit activations are stored shifted: stored
+    code = reference code - 128, stored zero point = reference zero point - 128.  The rounding then
+    happens on q + (zp - 128) instead of q + zp: the two fp32 sums can round differently only for
+    quotients within about 2^-17 of a tie."""
+    sc = q.quantizer.scale
+    if sc is None:
+        raise RuntimeError("fq_vit: activation quantizer is not calibrated")
+    if sc.numel() != 1:
+        raise NotImplementedError("W8A8 engine: only layer-wise activation scales are supported")
+    bt = q.quantizer.bit_type
+    if bt.bits != 8:
+        raise NotImplementedError("W8A8 engine: 8-bit activations only")
+    zp = q.quantizer.zero_point
+    z = 0 if zp is None else int(zp.reshape(-1)[0])
+    if not bt.signed:
+        z -= 128
+    if not -128 <= z <= 127:
+        raise NotImplementedError(f"W8A8 engine: zero point {z} outside the code range")
+    return float(sc.reshape(-1)[0]), z
+
+
 class W8A8Engine:
     """Fused HIP forward of a calibrated fq_vit encoder (quant mode), int8 codes end to end.
+
+    ``zero_points=True``: the zero-point engine -- int8 or uint8 ``BIT_TYPE_A`` and any layer-wise
+    activation zero point (omse calibration, the default ``Config``), on the ``_zp`` kernels only:
+    every quantiser is (scale, zp), each GEMM adds its layer's precomputed
+    ``col_offset = -zp_in * sum_k W[n, k]``, the 3x3 conv pads with the zero-point code, the attention
+    runs on the int8 V codes (no fp16 V copy).  One kernel chain (``row_lanes > 1`` is refused).
 
     Per block (all quantisers folded into the producing kernel):
       LN1+qact1 -> int8 | qkv GEMM + attn.qact1 -> int8 | attention (qact_attn1, rel-pos,
@@ -949,9 +1018,16 @@ class W8A8Engine:
     qacts.3 -> f32.  No im2col / pad copies.
     """
 
-    def __init__(self, enc: ImageEncoderViT):
+    def __init__(self, enc: ImageEncoderViT, zero_points: bool = False):
         from . import ops
         cfg = enc.cfg
+        self.zero_points = bool(zero_points)
+        if self.zero_points:
+            if cfg.BIT_TYPE_A.bits != 8 or cfg.INT_NORM or cfg.INT_SOFTMAX:
+                raise NotImplementedError("W8A8 zero-point engine supports Config(ptf=False, lis=False) with 8-bit "
+                                          "activations (int8 or uint8)")
+            self._init_zp(enc, ops)
+            return
         if not (cfg.BIT_TYPE_A.signed and cfg.BIT_TYPE_A.bits == 8) or cfg.INT_NORM or cfg.INT_SOFTMAX:
             raise NotImplementedError("W8A8 engine supports Config(ptf=False, lis=False) with BIT_TYPE_A=int8")
         self.enc = enc
@@ -1011,7 +1087,127 @@ class W8A8Engine:
                       enc.neck[3].eps)
         self.s_q = [_s(q) for q in enc.qacts]
 
-    def _weight(self, mod, tap_major: bool = False):
+    # ------------------------------------------------------------------ zero-point engine
+    def _init_zp(self, enc, ops):
+        self.enc = enc
+        self.ln_rpw = 1
+        self.row_lanes = 1
+        self.v16 = False          # the zero-point attention stages the int8 V codes
+        dev = enc.pos_embed.device
+        if dev.type != "cuda":
+            raise RuntimeError("W8A8 engine: move the encoder to the GPU first")
+        self.dev = dev
+        self.ops = ops
+        self.embed_dim = enc.patch_embed.proj.weight.shape[0]
+        self.patch = enc.patch_embed.proj.kernel_size[0]
+        if not enc.input_quant:
+            raise NotImplementedError("W8A8 engine: input_quant=False is not supported")
+        self.q_in = _sz(enc.qact_input)
+        self.patch_w = self._weight(enc.patch_embed.proj, zp_in=self.q_in[1])
+        self.q_pos = _sz(enc.qact_pos)
+        self.pos_codes = ops.quantize_zp(enc.pos_embed.detach().float().contiguous(), *self.q_pos).reshape(
+            -1, self.embed_dim)
+        self.q_pe = _sz(enc.patch_embed.qact)
+        self.q_x0 = _sz(enc.qact1)
+        self.blocks = []
+        for blk in enc.blocks:
+            a = blk.attn
+            q = dict(ln1=_sz(blk.qact1), qkv=_sz(a.qact1), a1=_sz(a.qact_attn1), a2=_sz(a.use_rel_pos_qact),
+                     ao=_sz(a.qact2), proj=_sz(a.qact3), x1=_sz(blk.qact2), ln2=_sz(blk.qact3), h=_sz(blk.mlp.qact1),
+                     l2=_sz(blk.mlp.qact2), x2=_sz(blk.qact4))
+            self.blocks.append(dict(
+                window=blk.window_size, heads=a.num_heads, scale=a.scale, q=q,
+                n1=(blk.norm1.weight.detach().float().contiguous(), blk.norm1.bias.detach().float().contiguous(),
+                    blk.norm1.eps),
+                n2=(blk.norm2.weight.detach().float().contiguous(), blk.norm2.bias.detach().float().contiguous(),
+                    blk.norm2.eps),
+                qkv=self._weight(a.qkv, zp_in=q["ln1"][1]), proj=self._weight(a.proj, zp_in=q["ao"][1]),
+                lin1=self._weight(blk.mlp.lin1, zp_in=q["ln2"][1]), lin2=self._weight(blk.mlp.lin2, zp_in=q["h"][1]),
+                relh=a.rel_pos_h.detach().float().contiguous(), relw=a.rel_pos_w.detach().float().contiguous(),
+                qkv_bias=a.qkv.bias.detach().float().contiguous() if a.qkv.bias is not None else None))
+        self.q_neck = [_sz(q) for q in enc.qacts]
+        self.neck0 = self._weight(enc.neck[0], zp_in=self.blocks[-1]["q"]["x2"][1] if self.blocks else self.q_x0[1])
+        self.neck2 = self._weight(enc.neck[2], tap_major=True, zp_in=self.q_neck[1][1])
+        self.pad16 = torch.full((16,), self.q_neck[1][1], dtype=torch.int8, device=dev)
+        self.ln_n1 = (enc.neck[1].weight.detach().float().contiguous(), enc.neck[1].bias.detach().float().contiguous(),
+                      enc.neck[1].eps)
+        self.ln_n3 = (enc.neck[3].weight.detach().float().contiguous(), enc.neck[3].bias.detach().float().contiguous(),
+                      enc.neck[3].eps)
+
+    def _gemm_zp(self, a, lw, epi, q_in, q_out, q_mid=None, res=None, q_res=None, out=None):
+        """One ``samq_i8_gemm_zp``: input codes under q_in, output under q_out, (Q8_RES) the mid
+        quantiser q_mid and residual codes under q_res; quantisers are (scale, zero point)."""
+        mid_s, mid_z = q_mid if q_mid is not None else (0.0, 0)
+        res_s, res_z = q_res if q_res is not None else (0.0, 0)
+        return self.ops.i8_gemm_zp(a, lw["packed"], lw["scale"], lw["n"], lw["bias"], epi, q_in[0], q_out[0], mid_s,
+                                   res_s, res, out, lw["cfg"], lw["col_offset"], mid_z, res_z, q_out[1])
+
+    @torch.no_grad()
+    def _forward_zp(self, img: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+        ops = self.ops
+        if self.row_lanes > 1:
+            raise NotImplementedError("W8A8 zero-point engine: one kernel chain only (row_lanes = 1)")
+
+        def tap(name, codes, q):
+            if taps is not None:
+                taps[name] = (codes.float() - q[1]) * q[0]
+        img = img.to(self.dev, torch.float32).contiguous()
+        b, cin, hh, ww = img.shape
+        p = self.patch
+        gh, gw = hh // p, ww // p
+        c = self.embed_dim
+        codes = ops.quantize_zp(img, *self.q_in)
+        pw = self.patch_w
+        if p == 16 and hh == ww:
+            x = ops.w8a8_conv_gemm_zp(codes, 1, pw["packed"], pw["scale"], pw["n"], pw["bias"], ops.EPI_Q8_RES,
+                                      self.q_in[0], self.q_x0[0], mid_scale=self.q_pe[0], res_scale=self.q_pos[0],
+                                      res=self.pos_codes, rmod=gh * gw, col_offset=pw["col_offset"],
+                                      mid_zp=self.q_pe[1], res_zp=self.q_pos[1], out_zp=self.q_x0[1]).view(b * gh * gw, c)
+        else:   # other patch geometries: explicit im2col
+            cols = codes.view(b, cin, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(b * gh * gw, cin * p * p)
+            x = ops.i8_gemm_zp(cols.contiguous(), pw["packed"], pw["scale"], pw["n"], pw["bias"], ops.EPI_Q8_RES,
+                               self.q_in[0], self.q_x0[0], self.q_pe[0], self.q_pos[0], self.pos_codes, None, pw["cfg"],
+                               pw["col_offset"], self.q_pe[1], self.q_pos[1], self.q_x0[1], rmod=gh * gw)
+        q_x = self.q_x0
+        tap("qact1", x.view(b, gh, gw, c), q_x)
+        xn = torch.empty_like(x)
+        ao = torch.empty_like(x)
+        for i, bl in enumerate(self.blocks):
+            pre = f"blocks.{i}."
+            q = bl["q"]
+            g1, b1, e1 = bl["n1"]
+            ops.layernorm_q_zp(x, g1, b1, e1, q_x[0], q["ln1"][0], q_x[1], q["ln1"][1], out=xn, rows_per_wave=self.ln_rpw)
+            tap(pre + "qact1", xn.view(b, gh, gw, c), q["ln1"])
+            qkv = self._gemm_zp(xn, bl["qkv"], ops.EPI_Q8, q["ln1"], q["qkv"]).view(b, gh, gw, 3 * c)
+            tap(pre + "attn.qact1", qkv, q["qkv"])
+            ops.rel_attention_q8_zp(qkv, bl["qkv_bias"], bl["relh"], bl["relw"], bl["heads"], bl["window"], bl["scale"],
+                                    q["qkv"][0], q["a1"][0], q["a2"][0], q["ao"][0], q["qkv"][1], q["a1"][1], q["a2"][1],
+                                    q["ao"][1], out=ao.view(b, gh, gw, c))
+            tap(pre + "attn.qact2", ao.view(b, gh, gw, c), q["ao"])
+            self._gemm_zp(ao, bl["proj"], ops.EPI_Q8_RES, q["ao"], q["x1"], q_mid=q["proj"], res=x, q_res=q_x, out=x)
+            tap(pre + "qact2", x.view(b, gh, gw, c), q["x1"])
+            g2, b2, e2 = bl["n2"]
+            ops.layernorm_q_zp(x, g2, b2, e2, q["x1"][0], q["ln2"][0], q["x1"][1], q["ln2"][1], out=xn,
+                               rows_per_wave=self.ln_rpw)
+            tap(pre + "qact3", xn.view(b, gh, gw, c), q["ln2"])
+            hbuf = self._gemm_zp(xn, bl["lin1"], ops.EPI_Q8_GELU, q["ln2"], q["h"])
+            tap(pre + "mlp.qact1", hbuf.view(b, gh, gw, -1), q["h"])
+            self._gemm_zp(hbuf, bl["lin2"], ops.EPI_Q8_RES, q["h"], q["x2"], q_mid=q["l2"], res=x, q_res=q["x1"], out=x)
+            q_x = q["x2"]
+            tap(pre + "qact4", x.view(b, gh, gw, c), q_x)
+        sq = self.q_neck
+        y0 = self._gemm_zp(x, self.neck0, ops.EPI_Q8, q_x, sq[0])
+        y1 = ops.layernorm_q_zp(y0, self.ln_n1[0], self.ln_n1[1], self.ln_n1[2], sq[0][0], sq[1][0], sq[0][1], sq[1][1])
+        oc = y1.shape[-1]
+        n2 = self.neck2
+        y2 = ops.w8a8_conv_gemm_zp(y1.view(b, gh, gw, oc).contiguous(), 2, n2["packed"], n2["scale"], n2["n"], n2["bias"],
+                                   ops.EPI_Q8, sq[1][0], sq[2][0], col_offset=n2["col_offset"], out_zp=sq[2][1],
+                                   pad16=self.pad16).view(b * gh * gw, -1)
+        y3 = ops.layernorm_q_zp(y2, self.ln_n3[0], self.ln_n3[1], self.ln_n3[2], sq[2][0], sq[3][0], sq[2][1], sq[3][1],
+                                out_dtype=torch.float32)
+        return y3.view(b, gh, gw, oc).permute(0, 3, 1, 2)
+
+    def _weight(self, mod, tap_major: bool = False, zp_in: Optional[int] = None):
         """Per-output-channel symmetric int8 codes of a QLinear / QConv2d weight (the reference's
         ``quantizer(self.weight)``, layers.py:196-199) packed for the int8 MFMA GEMM.
         ``tap_major``: conv weight flattened (n, ky, kx, c), the implicit 3x3 GEMM's K order."""
@@ -1025,8 +1221,11 @@ class W8A8Engine:
         # round(fp32(w / s)) with the correctly rounded fp32 quotient (uniform.py:31-36)
         codes = torch.clamp(torch.round((w2.double() / s.double()[:, None]).float()), -128, 127).to(torch.int8)
         bias = None if mod.bias is None else mod.bias.detach().float().contiguous()
-        return dict(packed=self.ops.w8_repack(codes), scale=s.contiguous(), bias=bias, n=n, k=w2.shape[1],
-                    cfg=0)   # i8 GEMM tile config (0: the library's pick)
+        lw = dict(packed=self.ops.w8_repack(codes), scale=s.contiguous(), bias=bias, n=n, k=w2.shape[1],
+                  cfg=0)   # i8 GEMM tile config (0: the library's pick)
+        if zp_in is not None:   # zero-point engine: the input zero point as an int32 offset per output column
+            lw["col_offset"] = self.ops.w8a8_col_offset(codes, zp_in)
+        return lw
 
     def _gemm(self, a, lw, epi, a_scale, out_scale, mid=0.0, res=None, res_scale=0.0, out=None):
         return self.ops.w8a8_gemm(a, lw["packed"], lw["scale"], lw["n"], lw["bias"], epi, a_scale, out_scale, mid,
@@ -1036,6 +1235,8 @@ class W8A8Engine:
     def forward(self, img: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         """``taps`` (debugging / tests): if a dict, receives the fake-quant f32 value of every
         inter-kernel activation under the reference QAct name that produced it."""
+        if self.zero_points:
+            return self._forward_zp(img, taps)
         ops = self.ops
 
         def tap(name, codes, s):

@@ -551,6 +551,131 @@ def w8a8_conv_gemm(x: torch.Tensor, mode: int, wpacked: torch.Tensor, wscale: to
     return out
 
 
+# ---- activation zero points: a quantiser is (scale, zp), code = clamp(rint(fl(x / s) + zp), -128, 127),
+# value = (code - zp) * s (fq_vit quantizer/uniform.py:23-45); zp an integer in [-128, 127]
+def _zp(*zps) -> None:
+    for z in zps:
+        assert int(z) == z and -128 <= z <= 127, f"zero point {z!r}: an integer in [-128, 127] expected"
+
+
+def quantize_zp(x: torch.Tensor, scale: float, zp: int, fake: bool = False,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``quantize`` with a zero point: int8 codes ``clamp(rint(x / s + zp), -128, 127)`` (the zero point
+    added to the fp32 quotient BEFORE the rounding) or, with ``fake``, the f32 value ``(code - zp) * s``."""
+    _need_cuda(x)
+    _zp(zp)
+    assert x.is_contiguous() and x.dtype in (torch.float32, torch.float16)
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32 if fake else torch.int8, device=x.device)
+    flags = (_lib.Q_IN_F16 if x.dtype == torch.float16 else 0) | (_lib.Q_OUT_FQ if fake else 0)
+    _lib.check(_lib.load().samq_quantize_zp(_ptr(x), _ptr(out), x.numel(), float(scale), int(zp), flags, _stream()),
+               "quantize_zp")
+    return out
+
+
+def layernorm_q_zp(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, in_scale: float = 0.0,
+                   out_scale: float = 0.0, zp_in: int = 0, zp_out: int = 0, out_dtype: torch.dtype = torch.int8,
+                   out: Optional[torch.Tensor] = None, rows_per_wave: int = 0) -> torch.Tensor:
+    """``layernorm_q`` with zero points: int8 input ``(code - zp_in) * in_scale``; int8 output codes of
+    the quantiser (out_scale, zp_out), or (out_dtype f32 with out_scale > 0) the fake-quant value
+    ``(code - zp_out) * out_scale``."""
+    _need_cuda(x, gamma, beta)
+    _zp(zp_in, zp_out)
+    c = x.shape[-1]
+    assert x.is_contiguous() and gamma.dtype == torch.float32 and beta.dtype == torch.float32
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    flags = 0
+    if x.dtype == torch.int8:
+        flags |= _lib.LN_IN_I8
+    elif x.dtype == torch.float16:
+        flags |= _lib.LN_IN_F16
+    if out.dtype == torch.int8:
+        flags |= _lib.LN_OUT_I8
+    elif out.dtype == torch.float32:
+        flags |= _lib.LN_OUT_F32 | (_lib.LN_OUT_I8 if out_scale > 0 else 0)
+    flags |= rows_per_wave << 16
+    _lib.check(_lib.load().samq_layernorm_q_zp(_ptr(x), _ptr(out), _ptr(gamma), _ptr(beta), x.numel() // c, c,
+                                               float(eps), flags, float(in_scale), float(out_scale), int(zp_in),
+                                               int(zp_out), _stream()), "layernorm_q_zp")
+    return out
+
+
+def _col_offset(col_offset: Optional[torch.Tensor], n: int) -> None:
+    if col_offset is not None:
+        assert col_offset.dtype == torch.int32 and col_offset.is_contiguous() and col_offset.numel() == n, \
+            "col_offset: int32 [N] expected"
+
+
+def w8a8_col_offset(w: torch.Tensor, zp_a: int) -> torch.Tensor:
+    """The zero-point GEMMs' ``col_offset`` of int8 weight codes w [N, K] under the input zero point
+    zp_a: int32 [N] = -zp_a * sum_k w[n, k] (exact: |sum| <= 128 K)."""
+    _zp(zp_a)
+    return (w.to(torch.int32).sum(1, dtype=torch.int32) * (-int(zp_a))).contiguous()
+
+
+def i8_gemm_zp(a: torch.Tensor, wpacked: torch.Tensor, wscale: torch.Tensor, n: int,
+               bias: Optional[torch.Tensor] = None, epilogue: int = EPI_Q8, a_scale: float = 1.0,
+               out_scale: float = 0.0, mid_scale: float = 0.0, res_scale: float = 0.0,
+               res: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, cfg: int = 0,
+               col_offset: Optional[torch.Tensor] = None, mid_zp: int = 0, res_zp: int = 0, out_zp: int = 0,
+               rmod: int = 0) -> torch.Tensor:
+    """``w8a8_gemm`` on activations with zero points (``samq_i8_gemm_zp``; W8 weights, epilogues Q8 /
+    Q8_GELU / Q8_RES): ``col_offset`` (int32 [N], ``w8a8_col_offset``) is added to every row's int32
+    sum before the scaling -- the input's zero point; the residual is ``(R - res_zp) * res_scale``
+    (row ``r % rmod`` of R when rmod > 0), the mid and output quantisers carry mid_zp / out_zp."""
+    _need_cuda(a, wpacked, wscale, bias, res, col_offset)
+    _zp(mid_zp, res_zp, out_zp)
+    assert a.dtype == torch.int8 and wscale.dtype == torch.float32
+    assert bias is None or bias.dtype == torch.float32
+    _col_offset(col_offset, n)
+    k = a.shape[-1]
+    a2 = a.reshape(-1, k)
+    out, o2 = _i8_out(a2, n, epilogue, out, tuple(a.shape[:-1]))
+    r2 = None if res is None else res.reshape(-1, n)
+    assert r2 is None or rmod == 0 or r2.shape[0] >= rmod, "i8_gemm_zp: the residual has fewer than rmod rows"
+    assert r2 is None or rmod > 0 or r2.shape[0] >= a2.shape[0], "i8_gemm_zp: the residual has fewer rows than A"
+    status = _lib.load().samq_i8_gemm_zp(
+        _ptr(a2), a2.stride(0), _ptr(wpacked), _ptr(wscale), _ptr(bias), _ptr(o2), o2.stride(0), _ptr(r2),
+        0 if r2 is None else r2.stride(0), a2.shape[0], n, k, epilogue, float(a_scale), float(mid_scale),
+        float(res_scale), float(out_scale), cfg, _ptr(col_offset), int(mid_zp), int(res_zp), int(out_zp), int(rmod),
+        _stream())
+    _lib.check(status, "i8_gemm_zp")
+    return out
+
+
+def w8a8_conv_gemm_zp(x: torch.Tensor, mode: int, wpacked: torch.Tensor, wscale: torch.Tensor, n: int,
+                      bias: Optional[torch.Tensor] = None, epilogue: int = EPI_Q8, a_scale: float = 1.0,
+                      out_scale: float = 0.0, mid_scale: float = 0.0, res_scale: float = 0.0,
+                      res: Optional[torch.Tensor] = None, rmod: int = 0, out: Optional[torch.Tensor] = None,
+                      col_offset: Optional[torch.Tensor] = None, mid_zp: int = 0, res_zp: int = 0, out_zp: int = 0,
+                      pad16: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``w8a8_conv_gemm`` on activations with zero points (``samq_w8a8_conv_gemm_zp``).  ``pad16`` (mode
+    2): 16 int8 device bytes, each the input's zero-point code -- what the 3x3 gather reads outside
+    the map (a padded 0.0 is the code zp), so ``col_offset`` holds for border pixels too."""
+    _need_cuda(x, wpacked, wscale, bias, res, col_offset, pad16)
+    _zp(mid_zp, res_zp, out_zp)
+    assert x.dtype == torch.int8 and x.is_contiguous() and wscale.dtype == torch.float32
+    _col_offset(col_offset, n)
+    assert pad16 is None or (pad16.dtype == torch.int8 and pad16.is_contiguous() and pad16.numel() >= 16), \
+        "pad16: 16 int8 bytes expected"
+    if mode == 1:
+        b, cin, side, _ = x.shape
+        g = side // 16
+    else:
+        b, g, _, cin = x.shape
+        side = g
+    assert res is None or res.numel() >= (rmod if rmod > 0 else b * g * g) * n, "w8a8_conv_gemm_zp: residual too small"
+    if out is None:
+        out = torch.empty((b, g, g, n), dtype=torch.int8, device=x.device)
+    assert out.is_cuda and out.dtype == torch.int8 and out.is_contiguous() and out.numel() == b * g * g * n
+    _lib.check(_lib.load().samq_w8a8_conv_gemm_zp(
+        _ptr(x), mode, b, cin, side, _ptr(wpacked), _ptr(wscale), _ptr(bias), _ptr(out), _ptr(res), rmod, n, epilogue,
+        float(a_scale), float(mid_scale), float(res_scale), float(out_scale), _ptr(col_offset), int(mid_zp),
+        int(res_zp), int(out_zp), _ptr(pad16), _stream()), "w8a8_conv_gemm_zp")
+    return out
+
+
 def w4a8_gemm(a, wpacked3, wscale, qzeros, n, bias=None, epilogue=EPI_BIAS, a_scale=1.0, out_scale=0.0,
               out=None, groupsize=-1, cfg=0, rowsum=None, rowsum_out=None):
     """GPTQ int4 weights (repacked layout 3) x int8 activation codes (cfg 0 = library pick).
@@ -620,6 +745,32 @@ def rel_attention_q8(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], rel_po
         _ptr(qkv), _ptr(qkv_bias), _ptr(rel_pos_h), _ptr(rel_pos_w), _ptr(out), b, h, w,
         heads, c // heads, window, float(sm_scale), float(s_qkv), float(s_a1), float(s_a2), float(s_out), int(r0),
         int(nr), _ptr(v16), _stream()), "rel_attention_q8")
+    return out
+
+
+def rel_attention_q8_zp(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], rel_pos_h: torch.Tensor,
+                        rel_pos_w: torch.Tensor, heads: int, window: int, sm_scale: float, s_qkv: float, s_a1: float,
+                        s_a2: float, s_out: float, zp_qkv: int, zp_a1: int, zp_a2: int, zp_out: int,
+                        out: Optional[torch.Tensor] = None, rows: Optional[tuple] = None,
+                        v16: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``rel_attention_q8`` on codes with zero points (``samq_rel_attention_q8_zp``): qkv codes under
+    (s_qkv, zp_qkv), score quantisers (s_a1, zp_a1) / (s_a2, zp_a2), output codes under (s_out, zp_out).
+    ``v16`` is refused (NotImplementedError): the 64 x 64 kernel runs on the int8 V codes."""
+    _need_cuda(qkv, qkv_bias, rel_pos_h, rel_pos_w, v16)
+    _zp(zp_qkv, zp_a1, zp_a2, zp_out)
+    b, h, w, c3 = qkv.shape
+    c = c3 // 3
+    assert qkv.dtype == torch.int8 and qkv.is_contiguous()
+    assert rel_pos_h.dtype == torch.float32 and rel_pos_w.dtype == torch.float32
+    assert qkv_bias is None or qkv_bias.dtype == torch.float32
+    if out is None:
+        out = torch.empty((b, h, w, c), dtype=torch.int8, device=qkv.device)
+    r0, nr = rows if rows is not None else (0, -1)
+    rel_pos_h, rel_pos_w = rel_pos_h.contiguous(), rel_pos_w.contiguous()   # named: see rel_attention
+    _lib.check(_lib.load().samq_rel_attention_q8_zp(
+        _ptr(qkv), _ptr(qkv_bias), _ptr(rel_pos_h), _ptr(rel_pos_w), _ptr(out), b, h, w,
+        heads, c // heads, window, float(sm_scale), float(s_qkv), float(s_a1), float(s_a2), float(s_out), int(r0),
+        int(nr), _ptr(v16), int(zp_qkv), int(zp_a1), int(zp_a2), int(zp_out), _stream()), "rel_attention_q8_zp")
     return out
 
 
