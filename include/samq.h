@@ -276,6 +276,53 @@ int samq_w8a8_conv_gemm_zp(const int8_t* x, int mode, int B, int Cin, int side, 
                            const int32_t* col_offset, int mid_zp, int res_zp, int out_zp, const int8_t* pad16,
                            hipStream_t stream);
 
+/* ---- Power-of-Two Factor activations (fq_vit observer/ptf.py; the QActs that feed a LayerNorm under
+ * Config(ptf=True)).  A PTF quantiser is (s0, zp, exp[C]): channel c has the scale s0 * 2^exp[c] with
+ * exp[c] in 0..3 and the layer's one zero point.  exp arrays are device uint8, 16-byte aligned.
+ * Powers of two keep everything exact: fl(x / (s0 2^e)) = fl(x / s0) 2^-e, and
+ * (code - zp) (s0 2^e) = ((code - zp) << e) s0.
+ *
+ * samq_layernorm_q_ptf: samq_layernorm_q_zp (SAMQ_LN_IN_I8 required) on an input under (in_scale,
+ * zp_in, in_exp[C]); in_exp must not be NULL.  Outputs as _zp (int8 codes or f32).
+ *
+ * samq_i8_gemm_ptf: samq_i8_gemm_zp with
+ *   out_exp [N]  (NULL = 0) the output quantiser's exponents: column n is quantised under
+ *                (out_scale * 2^out_exp[n], out_zp);
+ *   res_exp [N]  (NULL = 0, Q8_RES only) the residual's: ((R - res_zp) << res_exp[n]) * res_scale;
+ *   k_tiles_a, k_shift0..2  an INPUT with per-k exponents (Q8 only): A has k_tiles_a * 128 columns and K
+ *                is P * k_tiles_a * 128, P <= 4 -- wpacked is the repack of P masked copies of W stacked
+ *                along K, copy p holding W[n, k] where in_exp[k] == e_p (e_0 > e_1 > ... > e_{P-1} = 0)
+ *                and 0 elsewhere; the int32 sums are shifted left by k_shift[p] = e_p - e_{p+1} (1..3)
+ *                after pass p < P - 1, unused shifts are 0.  The result is sum_k a_k 2^in_exp[k] W[n, k];
+ *                col_offset[n] = -zp_a sum_k 2^in_exp[k] W[n, k].  P = 1: k_tiles_a = K / 128.
+ * Built for the tile configs the automatic pick returns for W8 weights (cfg 0, 82, 83, 84, 88, 89, 90);
+ * any other is SAMQ_ERR_UNSUPPORTED.  P = 1 with both arrays NULL equals samq_i8_gemm_zp bit for bit.
+ *
+ * samq_w8a8_conv_gemm_ptf: samq_w8a8_conv_gemm_zp with out_exp. */
+int samq_layernorm_q_ptf(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C,
+                         float eps, int flags, float in_scale, float out_scale, int zp_in, int zp_out,
+                         const uint8_t* in_exp, hipStream_t stream);
+int samq_i8_gemm_ptf(const int8_t* A, int64_t lda, const int8_t* wpacked, const float* wscale, const float* bias,
+                     void* C, int64_t ldc, const int8_t* R, int64_t ldr, int M, int N, int K, int epilogue,
+                     float a_scale, float mid_scale, float res_scale, float out_scale, int cfg,
+                     const int32_t* col_offset, int mid_zp, int res_zp, int out_zp, int rmod, const uint8_t* out_exp,
+                     const uint8_t* res_exp, int k_tiles_a, int k_shift0, int k_shift1, int k_shift2,
+                     hipStream_t stream);
+int samq_w8a8_conv_gemm_ptf(const int8_t* x, int mode, int B, int Cin, int side, const int8_t* wpacked,
+                            const float* wscale, const float* bias, void* C, const int8_t* R, int rmod, int N,
+                            int epilogue, float a_scale, float mid_scale, float res_scale, float out_scale,
+                            const int32_t* col_offset, int mid_zp, int res_zp, int out_zp, const int8_t* pad16,
+                            const uint8_t* out_exp, hipStream_t stream);
+
+/* The PTF observer's scores (observer/ptf.py:53-72) in one read of a row-major (rows, C) tensor (f32, or
+ * f16 with in_f16): sums[c][k] = sum_r (x - (clamp(rint(x / s_k + zp), qmin, qmax) - zp) s_k)^2 with
+ * s_k = scale1 * 2^k, k = 0..3; every f32 step as in samq_omse_scores, float64 sums in a fixed order.
+ * sums: double [C][4].  The workspace (samq_ptf_scores_workspace(rows, C) bytes, 8-byte aligned) is
+ * the caller's. */
+size_t samq_ptf_scores_workspace(int64_t rows, int C);
+int samq_ptf_scores(const void* x, int64_t rows, int C, int in_f16, float scale1, float zero_point, float qmin,
+                    float qmax, double* sums, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* samq_rel_attention_q8_rows on codes with zero points: qkv codes (s_qkv, zp_qkv), the two score
  * quantisers (s_a1, zp_a1) / (s_a2, zp_a2), output codes (s_out, zp_out).  q.k is
  * sum_d (q - zp_qkv)(k - zp_qkv), exact in int32; the rel-pos terms take (q - zp_qkv) s_qkv; the

@@ -23,6 +23,10 @@
 // = -zp_a * sum_k W[n, k] joins the sum before the scaling, the quantisers and the residual carry
 // their zero points.  The symmetric instantiations are untouched.
 //
+// Power-of-Two Factor activations (samq_i8_gemm_ptf, samq_w8a8_conv_gemm_ptf): the same kernels on
+// I8EpiPtf -- per-column exponents of the output quantiser and of the residual, and an input with
+// per-k exponents by masked-pass replay (gemm_i8_ring.h).  The I8EpiZp instantiations are untouched.
+//
 // The kernels: gemm_i8_ring.h (2- / 3-slot LDS ring, every weight format), gemm_i8_pp.h (W4
 // ping-pong), gemm_i8_epilogue.h (their shared epilogue).  Here: the W8 repack, the launchers, the
 // tile-config table and the C entry points.
@@ -55,6 +59,8 @@ struct I8Args {
   const float* bias; void* C; int64_t ldc; int M, N, K; I8Epi ep; I8Gather ga;
   // the _zp entries only (launch_i8<..., ZP = true>): the I8EpiZp fields beyond ep
   const int* col_offset = nullptr; float mid_zp = 0.f, res_zp = 0.f, out_zp = 0.f; const int8_t* pad16 = nullptr;
+  // the _ptf entries only (launch_i8_ptf): the I8EpiPtf fields beyond those
+  const uint8_t* out_exp = nullptr; const uint8_t* res_exp = nullptr; int k_tiles_a = 0; int k_shift[3] = {0, 0, 0};
 };
 
 template <int BM, int BN, int WMW, int WNW, int EPI, int BF, int ST, int AG = AG_ROWS, bool GRP = false, bool ZP = false>
@@ -76,6 +82,28 @@ static int launch_i8(const I8Args& a, hipStream_t st) {
                        a.A, a.lda, a.Wp, a.wscale, a.qzeros, a.bias, a.C, a.ldc, a.M, a.N, a.K, a.ep, a.ga);
   }
   SAMQ_LAUNCH_CHECK("i8_gemm launch");
+  return SAMQ_OK;
+}
+
+// W8 on Power-of-Two Factor activations (samq_i8_gemm_ptf / samq_w8a8_conv_gemm_ptf): the ring kernel on I8EpiPtf
+template <int BM, int BN, int WMW, int WNW, int EPI, int ST, int AG = AG_ROWS>
+static int launch_i8_ptf(const I8Args& a, hipStream_t st) {
+  const int nwg = ((a.M + BM - 1) / BM) * (a.N / BN);
+  I8EpiPtf ez;
+  static_cast<I8Epi&>(ez) = a.ep;
+  ez.col_offset = a.col_offset;
+  ez.mid_zp = a.mid_zp;
+  ez.res_zp = a.res_zp;
+  ez.out_zp = a.out_zp;
+  ez.pad16 = a.pad16;
+  ez.out_exp = a.out_exp;
+  ez.res_exp = a.res_exp;
+  ez.k_tiles_a = a.k_tiles_a;
+  for (int p = 0; p < 3; ++p) ez.k_shift[p] = a.k_shift[p];
+  hipLaunchKernelGGL((i8_gemm_kernel<BM, BN, WMW, WNW, EPI, BF_W8, ST, AG, false, I8EpiPtf>), dim3(nwg),
+                     dim3(64 * WMW * WNW), 0, st, a.A, a.lda, a.Wp, a.wscale, a.qzeros, a.bias, a.C, a.ldc, a.M, a.N,
+                     a.K, ez, a.ga);
+  SAMQ_LAUNCH_CHECK("i8_gemm_ptf launch");
   return SAMQ_OK;
 }
 
@@ -113,6 +141,17 @@ struct I8Ring {
   static int launch_zp(const I8Args& a, hipStream_t st) {   // W8, activations with zero points
     return launch_i8<BM, BN, WMW, WNW, EPI, BF_W8, ST8, AG_ROWS, false, true>(a, st);
   }
+  // W8, Power-of-Two Factor activations: instantiated for the tiles the automatic pick can return for
+  // W8 weights (cfg 89 / 84: 64x64, 90 / 88: 64x128, 82: 128x256, 83: 128x128 on three slots)
+  static constexpr bool PTF = (BM == 64 && BN == 64) || (BM == 64 && BN == 128) ||
+                              (BM == 128 && BN == 256 && WMW == 2 && WNW == 4) ||
+                              (BM == 128 && BN == 128 && WMW == 2 && WNW == 2 && ST8 == 3);
+  template <int EPI>
+  static int launch_ptf(const I8Args& a, hipStream_t st) {
+    if constexpr (PTF) return launch_i8_ptf<BM, BN, WMW, WNW, EPI, ST8>(a, st);
+    else return fail(SAMQ_ERR_UNSUPPORTED, "i8_gemm_ptf: this tile config is not built for PTF activations "
+                                           "(cfg 0, 82, 83, 84, 88, 89, 90 are)");
+  }
 };
 template <int BM, int BN, int WMW, int WNW, int ST>
 using I8RingG = I8Ring<BM, BN, WMW, WNW, ST, ST, true>;
@@ -134,6 +173,10 @@ struct I8Pp {
   static int launch_zp(const I8Args&, hipStream_t) {
     return fail(SAMQ_ERR_INVALID, "i8_gemm_zp: cfg " + std::to_string(ID) + " is the W4 ping-pong kernel");
   }
+  template <int EPI>
+  static int launch_ptf(const I8Args&, hipStream_t) {
+    return fail(SAMQ_ERR_INVALID, "i8_gemm_ptf: cfg " + std::to_string(ID) + " is the W4 ping-pong kernel");
+  }
 };
 
 struct I8NoTile {   // an id the table does not have
@@ -143,6 +186,8 @@ struct I8NoTile {   // an id the table does not have
   static int launch(const I8Args&, hipStream_t) { return fail(SAMQ_ERR_INVALID, "i8_gemm: unknown tile config"); }
   template <int EPI>
   static int launch_zp(const I8Args&, hipStream_t) { return fail(SAMQ_ERR_INVALID, "i8_gemm_zp: unknown tile config"); }
+  template <int EPI>
+  static int launch_ptf(const I8Args&, hipStream_t) { return fail(SAMQ_ERR_INVALID, "i8_gemm_ptf: unknown tile config"); }
 };
 
 // ---- the config table: f(row) for the row of tile config id cfg (f(I8NoTile) for any other id).
@@ -189,6 +234,12 @@ static int launch_i8_cfg(const I8Args& a, int cfg, hipStream_t st) {
 template <int EPI>
 static int launch_i8_cfg_zp(const I8Args& a, int cfg, hipStream_t st) {
   return with_i8_cfg(cfg, [&](auto row) { return decltype(row)::template launch_zp<EPI>(a, st); });
+}
+
+// W8 on Power-of-Two Factor activations (samq_i8_gemm_ptf)
+template <int EPI>
+static int launch_i8_cfg_ptf(const I8Args& a, int cfg, hipStream_t st) {
+  return with_i8_cfg(cfg, [&](auto row) { return decltype(row)::template launch_ptf<EPI>(a, st); });
 }
 
 // grouped W4 (ep.kpg K tiles per group)
@@ -424,6 +475,113 @@ extern "C" int samq_w8a8_conv_gemm_zp(const int8_t* x, int mode, int B, int Cin,
                             : launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8, BF_W8, 3, AG_3X3, false, true>(a, stream);
   return mode == AG_PATCH ? launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8_RES, BF_W8, 3, AG_PATCH, false, true>(a, stream)
                           : launch_i8<64, 64, 2, 2, SAMQ_EPI_Q8_RES, BF_W8, 3, AG_3X3, false, true>(a, stream);
+}
+
+// samq_i8_gemm_zp on Power-of-Two Factor activations.  K is the kernel's K = P * k_tiles_a * 128 (the
+// stacked masked weight copies, P <= 4); A has k_tiles_a * 128 columns.
+extern "C" int samq_i8_gemm_ptf(const int8_t* A, int64_t lda, const int8_t* wpacked, const float* wscale,
+                                const float* bias, void* C, int64_t ldc, const int8_t* R, int64_t ldr, int M, int N,
+                                int K, int epilogue, float a_scale, float mid_scale, float res_scale, float out_scale,
+                                int cfg, const int32_t* col_offset, int mid_zp, int res_zp, int out_zp, int rmod,
+                                const uint8_t* out_exp, const uint8_t* res_exp, int k_tiles_a, int k_shift0,
+                                int k_shift1, int k_shift2, hipStream_t stream) {
+  if (M == 0) return SAMQ_OK;   // empty batch: no work, data pointers may be null
+  SAMQ_REQUIRE(epilogue == SAMQ_EPI_Q8 || epilogue == SAMQ_EPI_Q8_GELU || epilogue == SAMQ_EPI_Q8_RES,
+               SAMQ_ERR_UNSUPPORTED, "i8_gemm_ptf: epilogue must be Q8, Q8_GELU or Q8_RES");
+  SAMQ_REQUIRE(A && wpacked && wscale && C, SAMQ_ERR_INVALID, "i8_gemm_ptf: null pointer");
+  SAMQ_REQUIRE(M >= 0 && N > 0 && K > 0 && K % 128 == 0, SAMQ_ERR_INVALID, "i8_gemm_ptf: K must be a multiple of 128");
+  SAMQ_REQUIRE(N % 64 == 0, SAMQ_ERR_INVALID, "i8_gemm_ptf: N must be a multiple of 64");
+  SAMQ_REQUIRE(k_tiles_a >= 1 && (K / 128) % k_tiles_a == 0 && K / 128 / k_tiles_a <= 4, SAMQ_ERR_INVALID,
+               "i8_gemm_ptf: K must be 1 to 4 passes over k_tiles_a tiles of 128");
+  const int passes = K / 128 / k_tiles_a;
+  const int64_t ka = (int64_t)k_tiles_a * 128;
+  const int shifts[3] = {k_shift0, k_shift1, k_shift2};
+  int total = 0;
+  for (int p = 0; p < 3; ++p) {
+    if (p < passes - 1) {
+      SAMQ_REQUIRE(shifts[p] >= 1 && shifts[p] <= 3, SAMQ_ERR_INVALID, "i8_gemm_ptf: k_shift of a pass must be in 1..3");
+      total += shifts[p];
+    } else {
+      SAMQ_REQUIRE(shifts[p] == 0, SAMQ_ERR_INVALID, "i8_gemm_ptf: k_shift beyond the passes must be 0");
+    }
+  }
+  SAMQ_REQUIRE(total <= 3, SAMQ_ERR_INVALID, "i8_gemm_ptf: the input exponents (the k_shift sum) must stay within 0..3");
+  SAMQ_REQUIRE(passes == 1 || epilogue == SAMQ_EPI_Q8, SAMQ_ERR_UNSUPPORTED,
+               "i8_gemm_ptf: input exponents (more than one pass) with the Q8 epilogue only");
+  SAMQ_REQUIRE(passes == 1 || ((int64_t)255 * 128 << total) * ka < ((int64_t)1 << 31), SAMQ_ERR_UNSUPPORTED,
+               "i8_gemm_ptf: 255 * 128 * 2^max_exp * K_A must stay below 2^31");
+  SAMQ_REQUIRE(lda >= ka && lda % 16 == 0 && ((uintptr_t)A & 15) == 0, SAMQ_ERR_INVALID,
+               "i8_gemm_ptf: A must be 16-byte aligned with lda >= k_tiles_a * 128, lda % 16 == 0");
+  SAMQ_REQUIRE(ldc >= N && ldc % 16 == 0 && ((uintptr_t)C & 15) == 0, SAMQ_ERR_INVALID,
+               "i8_gemm_ptf: C must be 16-byte aligned rows, ldc >= N");
+  SAMQ_REQUIRE(out_scale > 0.f, SAMQ_ERR_INVALID, "i8_gemm_ptf: needs out_scale > 0");
+  SAMQ_REQUIRE(epilogue != SAMQ_EPI_Q8_RES || (R && ldr >= N && ldr % 16 == 0 && ((uintptr_t)R & 15) == 0),
+               SAMQ_ERR_INVALID, "i8_gemm_ptf: Q8_RES needs a 16-byte aligned residual R with ldr >= N, ldr % 16 == 0");
+  SAMQ_REQUIRE(rmod >= 0, SAMQ_ERR_INVALID, "i8_gemm_ptf: rmod must be >= 0");
+  SAMQ_REQUIRE(((uintptr_t)out_exp & 15) == 0 && ((uintptr_t)res_exp & 15) == 0, SAMQ_ERR_INVALID,
+               "i8_gemm_ptf: out_exp / res_exp must be 16-byte aligned");
+  SAMQ_REQUIRE(!res_exp || epilogue == SAMQ_EPI_Q8_RES, SAMQ_ERR_INVALID, "i8_gemm_ptf: res_exp needs the Q8_RES epilogue");
+  if (cfg <= 0) cfg = i8_pick_cfg(M, N, BF_W8);
+  SAMQ_REQUIRE(i8_cfg_bn(cfg) > 0, SAMQ_ERR_INVALID, "i8_gemm_ptf: unknown tile config");
+  SAMQ_REQUIRE(N % i8_cfg_bn(cfg) == 0, SAMQ_ERR_INVALID, "i8_gemm_ptf: N not divisible by tile");
+  I8Args a{A, lda, (const char*)wpacked, wscale, nullptr, bias, C, ldc, M, N, K,
+           I8Epi{a_scale, mid_scale, res_scale, out_scale, R, ldr, rmod}, I8Gather{0, 0, 0}};
+  if (const int e = i8_zp_args(a, col_offset, mid_zp, res_zp, out_zp, "i8_gemm_ptf")) return e;
+  a.out_exp = out_exp;
+  a.res_exp = res_exp;
+  a.k_tiles_a = k_tiles_a;
+  for (int p = 0; p < 3; ++p) a.k_shift[p] = shifts[p];
+  switch (epilogue) {
+    case SAMQ_EPI_Q8: return launch_i8_cfg_ptf<SAMQ_EPI_Q8>(a, cfg, stream);
+    case SAMQ_EPI_Q8_GELU: return launch_i8_cfg_ptf<SAMQ_EPI_Q8_GELU>(a, cfg, stream);
+    default: return launch_i8_cfg_ptf<SAMQ_EPI_Q8_RES>(a, cfg, stream);
+  }
+}
+
+// samq_w8a8_conv_gemm_zp with the output quantiser's exponents (out_exp, uint8 [N], null = 0)
+extern "C" int samq_w8a8_conv_gemm_ptf(const int8_t* x, int mode, int B, int Cin, int side, const int8_t* wpacked,
+                                       const float* wscale, const float* bias, void* C, const int8_t* R, int rmod,
+                                       int N, int epilogue, float a_scale, float mid_scale, float res_scale,
+                                       float out_scale, const int32_t* col_offset, int mid_zp, int res_zp, int out_zp,
+                                       const int8_t* pad16, const uint8_t* out_exp, hipStream_t stream) {
+  if (B == 0) return SAMQ_OK;   // empty batch: no work, data pointers may be null
+  SAMQ_REQUIRE(x && wpacked && wscale && C, SAMQ_ERR_INVALID, "w8a8_conv_gemm_ptf: null pointer");
+  SAMQ_REQUIRE(mode == AG_PATCH || mode == AG_3X3, SAMQ_ERR_INVALID,
+               "w8a8_conv_gemm_ptf: mode must be 1 (patch) or 2 (3x3)");
+  SAMQ_REQUIRE(epilogue == SAMQ_EPI_Q8 || epilogue == SAMQ_EPI_Q8_RES, SAMQ_ERR_UNSUPPORTED,
+               "w8a8_conv_gemm_ptf: epilogue must be Q8 or Q8_RES");
+  SAMQ_REQUIRE(B > 0 && Cin > 0 && side > 0 && N > 0 && N % 64 == 0, SAMQ_ERR_INVALID, "w8a8_conv_gemm_ptf: bad shape");
+  SAMQ_REQUIRE(out_scale > 0.f, SAMQ_ERR_INVALID, "w8a8_conv_gemm_ptf: needs out_scale > 0");
+  SAMQ_REQUIRE(epilogue != SAMQ_EPI_Q8_RES || (R && ((uintptr_t)R & 15) == 0), SAMQ_ERR_INVALID,
+               "w8a8_conv_gemm_ptf: Q8_RES needs a 16-byte aligned residual");
+  SAMQ_REQUIRE(rmod >= 0, SAMQ_ERR_INVALID, "w8a8_conv_gemm_ptf: rmod must be >= 0");
+  SAMQ_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)C & 15) == 0 && ((uintptr_t)out_exp & 15) == 0, SAMQ_ERR_INVALID,
+               "w8a8_conv_gemm_ptf: operands and out_exp must be 16-byte aligned");
+  SAMQ_REQUIRE(mode != AG_3X3 || (pad16 && ((uintptr_t)pad16 & 15) == 0), SAMQ_ERR_INVALID,
+               "w8a8_conv_gemm_ptf: 3x3 mode needs pad16, 16 bytes of the input's zero-point code, 16-byte aligned");
+  int G, K;
+  if (mode == AG_PATCH) {
+    SAMQ_REQUIRE(side % 16 == 0 && (Cin * 256) % 128 == 0, SAMQ_ERR_UNSUPPORTED,
+                 "w8a8_conv_gemm_ptf: patch mode is the 16x16 / stride 16 PatchEmbed");
+    G = side / 16;
+    K = Cin * 256;
+  } else {
+    SAMQ_REQUIRE(Cin % 128 == 0, SAMQ_ERR_UNSUPPORTED, "w8a8_conv_gemm_ptf: 3x3 mode needs Cin % 128 == 0");
+    G = side;
+    K = 9 * Cin;
+  }
+  const int M = B * G * G;
+  I8Args a{x, K, (const char*)wpacked, wscale, nullptr, bias, C, N, M, N, K,
+           I8Epi{a_scale, mid_scale, res_scale, out_scale, R, N, rmod}, I8Gather{side, G, Cin}};
+  if (const int e = i8_zp_args(a, col_offset, mid_zp, res_zp, out_zp, "w8a8_conv_gemm_ptf")) return e;
+  a.pad16 = pad16;
+  a.out_exp = out_exp;
+  a.k_tiles_a = K / 128;
+  if (epilogue == SAMQ_EPI_Q8)
+    return mode == AG_PATCH ? launch_i8_ptf<64, 64, 2, 2, SAMQ_EPI_Q8, 3, AG_PATCH>(a, stream)
+                            : launch_i8_ptf<64, 64, 2, 2, SAMQ_EPI_Q8, 3, AG_3X3>(a, stream);
+  return mode == AG_PATCH ? launch_i8_ptf<64, 64, 2, 2, SAMQ_EPI_Q8_RES, 3, AG_PATCH>(a, stream)
+                          : launch_i8_ptf<64, 64, 2, 2, SAMQ_EPI_Q8_RES, 3, AG_3X3>(a, stream);
 }
 
 extern "C" int samq_w8a8_gemm(const int8_t* A, int64_t lda, const int8_t* wpacked, const float* wscale,

@@ -42,6 +42,26 @@ struct I8EpiZp : I8Epi {
   const int8_t* pad16;
 };
 
+// Power-of-Two Factor activations (samq_i8_gemm_ptf / samq_w8a8_conv_gemm_ptf): a PTF quantiser is
+// (s0, zp, exp[C]) with the channel's scale s0 * 2^exp[c], exp[c] in 0..3 (fq_vit observer/ptf.py).
+// The kernels instantiated on I8EpiPtf take, beside the I8EpiZp fields,
+//   out_exp   uint8 [N] (null = 0): the OUTPUT quantiser's exponents.  x * 2^-e is exact and
+//             fl(x / (s * 2^e)) = fl(x / s) * 2^-e, so the unchanged quotient chain runs on x * 2^-e;
+//   res_exp   uint8 [N] (null = 0, Q8_RES): the residual value is ((R - res_zp) << e) * res_scale;
+//   k_tiles_a / k_shift  the INPUT's exponents along K by masked-pass replay (gemm_i8_ring.h): A has
+//             k_tiles_a K tiles, the kernel's K is P * k_tiles_a * 128 over P stacked masked weight
+//             copies; after the last tile of pass p < P - 1 the int32 sums are shifted left by k_shift[p].
+// Both arrays null and P = 1: bit-identical to the I8EpiZp kernels.
+struct I8EpiPtf : I8EpiZp {
+  const uint8_t* out_exp;
+  const uint8_t* res_exp;
+  int k_tiles_a;
+  int k_shift[3];
+};
+
+// 2^e (e in -3..3) as a float, built in the exponent field
+__device__ __forceinline__ float ptf_pow2(int e) { return __builtin_bit_cast(float, (uint32_t)(127 + e) << 23); }
+
 // The W4 unpack of both kernels: four nibbles q (one per byte) minus the zero point zpx (zp in
 // every byte) as int8 -- bytes(q) | 0x80 minus zp per byte never borrows, ^0x80 -> int8
 __device__ __forceinline__ int w4_to_i8(uint32_t nib, uint32_t zpx) {
@@ -70,7 +90,8 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
                                                   const float4_t* xcur = nullptr, float4_t* xnext = nullptr,
                                                   const float* scb = nullptr) {
   constexpr bool RESB = EPI == SAMQ_EPI_RESADD_F32;
-  constexpr bool ZP = std::is_same<EpiArgs, I8EpiZp>::value;   // activations with zero points
+  constexpr bool ZP = std::is_base_of<I8EpiZp, EpiArgs>::value;   // activations with zero points
+  constexpr bool PTF = std::is_same<EpiArgs, I8EpiPtf>::value;    // ... and per-column power-of-two factors
   static_assert(!ZP || (!ZPS && (EPI == SAMQ_EPI_Q8 || EPI == SAMQ_EPI_Q8_GELU || EPI == SAMQ_EPI_Q8_RES)),
                 "zero points: W8 weights, int8-code epilogues");
   const int hsel = lane >> 5;
@@ -207,6 +228,12 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
             if (EPI == SAMQ_EPI_Q8_RES)
               res = *(const u32x4*)(ep_args.R + (int64_t)(ep_args.rmod > 0 ? row % ep_args.rmod : row) * ep_args.ldr +
                                     col_base + 16 * c16);
+            u32x4 oexp = {0u, 0u, 0u, 0u}, rexp = {0u, 0u, 0u, 0u};   // PTF: the 16 columns' exponent bytes
+            if constexpr (PTF) {
+              if (ep_args.out_exp) oexp = *(const u32x4*)(ep_args.out_exp + col_base + 16 * c16);
+              if (EPI == SAMQ_EPI_Q8_RES && ep_args.res_exp)
+                rexp = *(const u32x4*)(ep_args.res_exp + col_base + 16 * c16);
+            }
             u32x4 o;
             float vq[EPI == SAMQ_EPI_Q8 ? 16 : 1];
 #pragma unroll
@@ -220,11 +247,18 @@ __device__ __forceinline__ void i8_epilogue_slice(int i, const AccV (&acc)[TM][T
                     if (ep_args.mid_scale > 0.f)
                       x = (q8_exact2_zp(x, ep_args.mid_scale, inv_mid, lim_mid, zp_mid) - (float2_t)(zp_mid)) *
                           ep_args.mid_scale;
-                    const float2_t rv = (float2_t{(float)(int8_t)((res[w] >> (8 * b)) & 0xFFu),
-                                                  (float)(int8_t)((res[w] >> (8 * b + 8)) & 0xFFu)} -
-                                         (float2_t)(zp_res)) * ep_args.res_scale;   // code - zp: exact
+                    float2_t rc = float2_t{(float)(int8_t)((res[w] >> (8 * b)) & 0xFFu),
+                                           (float)(int8_t)((res[w] >> (8 * b + 8)) & 0xFFu)} -
+                                  (float2_t)(zp_res);   // code - zp: exact
+                    if constexpr (PTF)                  // (code - zp) << e: exact
+                      rc = rc * float2_t{ptf_pow2((int)((rexp[w] >> (8 * b)) & 3u)),
+                                         ptf_pow2((int)((rexp[w] >> (8 * b + 8)) & 3u))};
+                    const float2_t rv = rc * ep_args.res_scale;
                     x = rv + x;
                   }
+                  if constexpr (PTF)   // the column's output scale is out_scale * 2^e
+                    x = x * float2_t{ptf_pow2(-(int)((oexp[w] >> (8 * b)) & 3u)),
+                                     ptf_pow2(-(int)((oexp[w] >> (8 * b + 8)) & 3u))};
                   // Q8_GELU: the reciprocal-multiply quotient as in the symmetric kernel (q8_recip2), the
                   // zero point added before the rounding; q8_pack4 saturates
                   const float2_t q = EPI == SAMQ_EPI_Q8_GELU ? q8_recip2(x, inv_out, zp_out)

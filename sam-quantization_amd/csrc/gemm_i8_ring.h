@@ -39,6 +39,13 @@ __device__ __forceinline__ void vm_wait_i8() {
 // EpiArgs = I8EpiZp (W8 only): activations with zero points -- the epilogue adds col_offset and
 // carries the quantisers' zero points, the 3x3 gather pads with the zero-point code (I8EpiZp,
 // gemm_i8_epilogue.h); the main loop is the same.
+// EpiArgs = I8EpiPtf: Power-of-Two Factor activations.  Epilogue: per-column exponents of the output
+// quantiser and the residual.  Main loop (AG_ROWS): masked-pass replay for an INPUT with per-k
+// exponents -- A has ep_args.k_tiles_a K tiles and the kernel's K runs P <= 4 times over them (the A
+// tile index is a running counter modulo k_tiles_a) against P stacked weight copies, pass p holding
+// W[n, k] where exp[k] == e_p (descending, the last 0) and 0 elsewhere; after the last tile of pass
+// p < P - 1 the int32 sums are shifted left by k_shift[p] = e_p - e_{p+1} (Horner), which gives
+// sum_k a_k 2^exp[k] W[n, k] exactly (the host checks 255 * 128 * 2^max_exp * K_A < 2^31).
 template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int BFMT, int STAGES, int AG = AG_ROWS, bool GRP = false,
           typename EpiArgs = I8Epi>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N)
@@ -46,7 +53,8 @@ void i8_gemm_kernel(const int8_t* __restrict__ A, int64_t lda, const char* __res
                     const float* __restrict__ wscale, const uint32_t* __restrict__ qzeros,
                     const float* __restrict__ bias, void* __restrict__ Cout, int64_t ldc,
                     int M, int N, int K, EpiArgs ep_args, I8Gather ga) {
-  constexpr bool ZP = std::is_same<EpiArgs, I8EpiZp>::value;
+  constexpr bool ZP = std::is_base_of<I8EpiZp, EpiArgs>::value;
+  constexpr bool PTF = std::is_same<EpiArgs, I8EpiPtf>::value;
   static_assert(!ZP || (BFMT == BF_W8 && !GRP), "zero points: W8 weights");
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int WM = BM / WAVES_M;
@@ -122,10 +130,19 @@ void i8_gemm_kernel(const int8_t* __restrict__ A, int64_t lda, const char* __res
     }
     return (const char*)(A + (((int64_t)b * ga.G + sy) * ga.G + sx) * ga.Cin + c0);
   };
+  int ka_next = 0;   // PTF: the A tile of the next issue, kt mod k_tiles_a (issue runs kt = 0, 1, 2, ...)
   auto issue = [&](int kt, int slot) {
+    int ka = kt;
+    if constexpr (PTF) {
+      ka = ka_next;
+      ka_next = ka_next + 1 == ep_args.k_tiles_a ? 0 : ka_next + 1;
+    }
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
       const char* p = src[i] + kt * step[i];
+      if constexpr (PTF) {
+        if (wave * NPW + i < NA) p = src[i] + ka * step[i];
+      }
       if (AG != AG_ROWS && wave * NPW + i < NA) p = a_gather(i, kt);
       __builtin_amdgcn_global_load_lds((const SAMQ_GLOBAL void*)p, (SAMQ_LDS void*)(smem + slot * STAGE + dst[i]), 16,
                                        0, 0);
@@ -178,6 +195,7 @@ void i8_gemm_kernel(const int8_t* __restrict__ A, int64_t lda, const char* __res
   uint32_t kLo = 0x0F0F0F0Fu;
   asm volatile("" : "+v"(kLo));
 
+  int ptile = 0, pass = 0;   // PTF: tiles done in the current pass, the pass
   issue(0, 0);
   if (STAGES > 2 && kt_count > 1) issue(1, 1);
   int slot = 0;
@@ -243,6 +261,21 @@ void i8_gemm_kernel(const int8_t* __restrict__ A, int64_t lda, const char* __res
         }
 #pragma unroll
         for (int i = 0; i < TM; ++i) acc[i][t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[i], bf, acc[i][t], 0, 0, 0);
+      }
+    }
+    if constexpr (PTF) {   // end of a pass that is not the last: the sums move up to the next exponent
+      if (++ptile == ep_args.k_tiles_a) {
+        ptile = 0;
+        if (kt + 1 < kt_count) {
+          const int sh = pass == 0 ? ep_args.k_shift[0] : (pass == 1 ? ep_args.k_shift[1] : ep_args.k_shift[2]);
+          ++pass;
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int t = 0; t < TN; ++t)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) acc[i][t][r] = (int)((uint32_t)acc[i][t][r] << sh);
+        }
       }
     }
     if (GRP && ((kt + 1) % kpg == 0 || kt + 1 == kt_count)) {   // group end: scale the exact sums in

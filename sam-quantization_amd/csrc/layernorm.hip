@@ -22,7 +22,10 @@ __device__ __forceinline__ float ln_q8(float v, float s) {   // fq_vit uniform.p
 // place); ``xin`` (const restrict) is the input of the ADD == 0 variants only.
 // ZP (samq_layernorm_q_zp): int8 input (code - zp_in) * in_scale, the subtraction in integers; the
 // output quantiser (out_scale, zp_out) with the fake-quant value (code - zp_out) * out_scale.
-template <int IN, int OUT, int VPT, int RPW, int ADD = 0, bool ZP = false>
+// PTF (samq_layernorm_q_ptf; ZP, int8 input): the input quantiser's scale is in_scale * 2^exp[c], exp a
+// uint8 [C] array in 0..3: x = ((code - zp_in) << exp[c]) * in_scale.  A lane's 4 channels take one
+// dword of exponents.  The array travels in ``delta``, which only the ADD variants read.
+template <int IN, int OUT, int VPT, int RPW, int ADD = 0, bool ZP = false, bool PTF = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__ xin, void* __restrict__ y,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int64_t rows, int C,
@@ -33,6 +36,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
                                                         int* __restrict__ rs_zero = nullptr, int zp_in = 0,
                                                         float zp_out = 0.f) {
   static_assert(ADD == 0 || IN == LN_F32, "residual add: f32 rows");
+  static_assert(!PTF || (ZP && IN == LN_I8 && ADD == 0), "power-of-two factors: int8 input with a zero point");
   const int lane = threadIdx.x & 63;
   const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
   if (row0 >= rows) return;
@@ -51,9 +55,13 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
           v[r][i] = float4_t{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
         } else if (IN == LN_I8) {
           const uint32_t w = ((const uint32_t*)xin)[row * nvec + j];
+          uint32_t ew = 0;
+          if constexpr (PTF) ew = ((const uint32_t*)delta)[j];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            if constexpr (ZP) v[r][i][e] = (float)((int)(int8_t)((w >> (8 * e)) & 0xFFu) - zp_in) * in_scale;
+            if constexpr (PTF)   // (code - zp) << exp: |.| <= 255 * 8, exact
+              v[r][i][e] = (float)(((int)(int8_t)((w >> (8 * e)) & 0xFFu) - zp_in) * (1 << ((ew >> (8 * e)) & 3u))) * in_scale;
+            else if constexpr (ZP) v[r][i][e] = (float)((int)(int8_t)((w >> (8 * e)) & 0xFFu) - zp_in) * in_scale;
             else v[r][i][e] = (float)(int8_t)((w >> (8 * e)) & 0xFFu) * in_scale;
           }
         } else {
@@ -281,6 +289,55 @@ extern "C" int samq_layernorm_q_zp(const void* x, void* y, const float* gamma, c
                                            : ((flags & SAMQ_LN_OUT_F32) ? LN_F32 : LN_F16);
   return ln_launch(x, y, gamma, beta, rows, C, eps, in, out, in_scale, out_scale, ln_rpw(flags), stream, nullptr,
                    nullptr, nullptr, true, zp_in, zp_out);
+}
+
+// samq_layernorm_q_zp on an int8 input under a Power-of-Two Factor quantiser (fq_vit observer/ptf.py):
+// x = ((code - zp_in) << in_exp[c]) * in_scale, in_exp uint8 [C] in 0..3.  Outputs as _zp: int8 codes,
+// f32 fake-quant or plain f32.
+template <int O, int V, int R>
+static void ln_ptf_launch(dim3 grid, hipStream_t stream, const void* x, void* y, const float* gamma, const float* beta,
+                          int64_t rows, int C, float eps, float in_scale, float out_scale, int zp_in, int zp_out,
+                          const uint8_t* in_exp) {
+  hipLaunchKernelGGL((layernorm_kernel<LN_I8, O, V, R, 0, true, true>), grid, dim3(256), 0, stream, x, y, gamma, beta,
+                     rows, C, eps, in_scale, out_scale, nullptr, (const void*)in_exp, nullptr, nullptr, nullptr, zp_in,
+                     (float)zp_out);
+}
+
+extern "C" int samq_layernorm_q_ptf(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C,
+                                    float eps, int flags, float in_scale, float out_scale, int zp_in, int zp_out,
+                                    const uint8_t* in_exp, hipStream_t stream) {
+  SAMQ_REQUIRE((flags & SAMQ_LN_IN_I8) != 0, SAMQ_ERR_INVALID, "layernorm_q_ptf: int8 input only (SAMQ_LN_IN_I8)");
+  SAMQ_REQUIRE(in_exp && ((uintptr_t)in_exp & 15) == 0, SAMQ_ERR_INVALID,
+               "layernorm_q_ptf: in_exp must be a 16-byte aligned array of C bytes");
+  SAMQ_REQUIRE(in_scale > 0.f, SAMQ_ERR_INVALID, "layernorm_q_ptf: in_scale must be > 0");
+  SAMQ_REQUIRE(!(flags & SAMQ_LN_OUT_I8) || out_scale > 0.f, SAMQ_ERR_INVALID, "layernorm_q_ptf: out_scale must be > 0");
+  SAMQ_REQUIRE((flags & (SAMQ_LN_OUT_I8 | SAMQ_LN_OUT_F32)) != 0, SAMQ_ERR_UNSUPPORTED,
+               "layernorm_q_ptf: int8-code or f32 output");
+  SAMQ_REQUIRE(zp_in >= -128 && zp_in <= 127 && zp_out >= -128 && zp_out <= 127, SAMQ_ERR_INVALID,
+               "layernorm_q_ptf: zero points must be in [-128, 127]");
+  if (rows == 0) return SAMQ_OK;   // empty batch: no work, data pointers may be null
+  SAMQ_REQUIRE(x && y && gamma && beta, SAMQ_ERR_INVALID, "layernorm_q_ptf: null pointer");
+  SAMQ_REQUIRE(C > 0 && C % 4 == 0 && C <= 4096, SAMQ_ERR_INVALID, "layernorm_q_ptf: C must be a multiple of 4, <= 4096");
+  if (rows <= 0) return SAMQ_OK;
+  int rpw = ln_rpw(flags);
+  SAMQ_REQUIRE(rpw == 1 || rpw == 2 || rpw == 4, SAMQ_ERR_INVALID, "layernorm_q_ptf: rows per wave must be 1, 2 or 4");
+  const int vpt = (C / 4 + 63) / 64;
+  if (vpt > 5) rpw = 1;
+  const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
+  const int out = (flags & SAMQ_LN_OUT_I8) ? ((flags & SAMQ_LN_OUT_F32) ? LN_FQ32 : LN_I8) : LN_F32;
+#define LNP(O, V, R) ln_ptf_launch<O, V, R>(grid, stream, x, y, gamma, beta, rows, C, eps, in_scale, out_scale, zp_in, zp_out, in_exp)
+#define LNP_R(O, V) do { if (rpw == 1) LNP(O, V, 1); else if (rpw == 2) LNP(O, V, 2); else LNP(O, V, 4); } while (0)
+#define LNP_V(O) \
+  do { \
+    if (vpt <= 1) LNP_R(O, 1); else if (vpt <= 3) LNP_R(O, 3); else if (vpt <= 4) LNP_R(O, 4); \
+    else if (vpt <= 5) LNP_R(O, 5); else LNP(O, 16, 1); \
+  } while (0)
+  if (out == LN_I8) LNP_V(LN_I8); else if (out == LN_FQ32) LNP_V(LN_FQ32); else LNP_V(LN_F32);
+#undef LNP_V
+#undef LNP_R
+#undef LNP
+  SAMQ_LAUNCH_CHECK("layernorm_q_ptf launch");
+  return SAMQ_OK;
 }
 
 // LN-q with the output rows' code sums (round 6): rowsum[r] = sum_c y[r, c] (int8 codes, SAMQ_LN_OUT_I8

@@ -308,6 +308,67 @@ __global__ __launch_bounds__(64) void omse_fold_kernel(const double* __restrict_
   if (threadIdx.x == 0) sums[c] = a;
 }
 
+// ---------------------------------------------------------------- ptf per-channel scores
+// PtfObserver.get_quantization_params (observer/ptf.py:53-72): for every channel c of a row-major
+// (rows, C) tensor the four sums over the rows of (x - fq_k(x))^2 under the scales s1 * {1, 2, 4, 8} and
+// one zero point, each term in f32 as in omse_scores_kernel.  A workgroup takes 64 channels (a lane a
+// column: coalesced rows) and one slab of rows, its four waves every fourth row of the slab; a lane's
+// float64 sums fold through LDS in wave order into partial[slab][c][k].
+constexpr int PTF_MAX_SLABS = 256;
+
+template <bool F16>
+__global__ __launch_bounds__(256) void ptf_scores_kernel(const void* __restrict__ x, int64_t rows, int C,
+                                                         int64_t rows_per_slab, float s1, float zp, float qmin,
+                                                         float qmax, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  __shared__ double wsum[4][64][4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 64 + lane;
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_slab;
+  const int64_t r1 = r0 + rows_per_slab < rows ? r0 + rows_per_slab : rows;
+  const float sc[4] = {s1, s1 * 2.0f, s1 * 4.0f, s1 * 8.0f};   // exact doublings (ptf.py halves scale8 three times)
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  if (c < C) {
+    for (int64_t r = r0 + wave; r < r1; r += 4) {
+      const float v = mm_load<F16>(x, r * C + c);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float q = fminf(fmaxf(__builtin_rintf(v / sc[k] + zp), qmin), qmax);
+        const float xq = (q - zp) * sc[k];
+        const float d = v - xq;
+        acc[k] += (double)(d * d);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) wsum[wave][lane][k] = acc[k];
+  __syncthreads();
+  if (wave == 0 && c < C) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      partial[((int64_t)blockIdx.y * C + c) * 4 + k] = (wsum[0][lane][k] + wsum[1][lane][k]) +
+                                                       (wsum[2][lane][k] + wsum[3][lane][k]);
+  }
+}
+
+// the slabs' sums of one (channel, scale) in slab order
+__global__ __launch_bounds__(256) void ptf_fold_kernel(const double* __restrict__ partial, int slabs, int64_t n4,
+                                                       double* __restrict__ sums) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  double a = 0.0;
+  for (int s = 0; s < slabs; ++s) a += partial[(int64_t)s * n4 + i];
+  sums[i] = a;
+}
+
+static int ptf_slabs(int64_t rows, int C) {
+  const int64_t col_blocks = (C + 63) / 64;
+  int64_t s = (1024 + col_blocks - 1) / col_blocks;     // ~1 K workgroups
+  const int64_t max_s = (rows + 31) / 32;               // at least 32 rows each
+  s = s < max_s ? s : max_s;
+  return (int)(s < 1 ? 1 : (s > PTF_MAX_SLABS ? PTF_MAX_SLABS : s));
+}
+
 static int os_grid(int64_t n) {
   const int64_t g = (n + 256 * 16 - 1) / (256 * 16);   // at least 16 elements per thread
   return (int)(g < 1 ? 1 : (g > OS_MAX_GRID ? OS_MAX_GRID : g));
@@ -429,5 +490,42 @@ extern "C" int samq_omse_scores(const void* x, int64_t n, int in_f16, const floa
   SAMQ_LAUNCH_CHECK("omse_scores launch");
   hipLaunchKernelGGL(omse_fold_kernel, dim3(ncand), dim3(64), 0, stream, partial, blocks, sums);
   SAMQ_LAUNCH_CHECK("omse_scores fold launch");
+  return SAMQ_OK;
+}
+
+// The PTF observer's per-channel scores in one read of a row-major (rows, C) tensor (f32, or f16 with
+// in_f16): sums[c][k] = sum_r (x[r, c] - fq_k(x[r, c]))^2 for the scales scale1 * 2^k, k = 0..3, and the
+// shared zero point, each term in f32 exactly as torch's separate ops round it (observer/ptf.py:55-70),
+// summed in float64 in a fixed order (the caller divides by rows).  sums is double [C][4]; the
+// workspace (samq_ptf_scores_workspace(rows, C) bytes, 8-byte aligned) is the caller's.
+extern "C" size_t samq_ptf_scores_workspace(int64_t rows, int C) {
+  if (rows <= 0 || C <= 0) return 0;
+  return (size_t)ptf_slabs(rows, C) * (size_t)C * 4 * sizeof(double);
+}
+
+extern "C" int samq_ptf_scores(const void* x, int64_t rows, int C, int in_f16, float scale1, float zero_point,
+                               float qmin, float qmax, double* sums, void* workspace, size_t workspace_bytes,
+                               hipStream_t stream) {
+  SAMQ_REQUIRE(x && sums, SAMQ_ERR_INVALID, "ptf_scores: null pointer");
+  SAMQ_REQUIRE(rows > 0 && C > 0, SAMQ_ERR_INVALID, "ptf_scores: empty tensor");
+  SAMQ_REQUIRE(scale1 > 0.f, SAMQ_ERR_INVALID, "ptf_scores: scale1 must be > 0");
+  SAMQ_REQUIRE(qmin <= qmax, SAMQ_ERR_INVALID, "ptf_scores: qmin > qmax");
+  const int slabs = ptf_slabs(rows, C);
+  SAMQ_REQUIRE(workspace && workspace_bytes >= (size_t)slabs * (size_t)C * 4 * sizeof(double) &&
+                   ((uintptr_t)workspace & 7) == 0,
+               SAMQ_ERR_INVALID, "ptf_scores: workspace smaller than samq_ptf_scores_workspace() or misaligned");
+  const int64_t rps = (rows + slabs - 1) / slabs;
+  double* partial = (double*)workspace;
+  const dim3 grid((unsigned)((C + 63) / 64), (unsigned)slabs);
+  if (in_f16)
+    hipLaunchKernelGGL((ptf_scores_kernel<true>), grid, dim3(256), 0, stream, x, rows, C, rps, scale1, zero_point, qmin,
+                       qmax, partial);
+  else
+    hipLaunchKernelGGL((ptf_scores_kernel<false>), grid, dim3(256), 0, stream, x, rows, C, rps, scale1, zero_point, qmin,
+                       qmax, partial);
+  SAMQ_LAUNCH_CHECK("ptf_scores launch");
+  const int64_t n4 = (int64_t)C * 4;
+  hipLaunchKernelGGL(ptf_fold_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, partial, slabs, n4, sums);
+  SAMQ_LAUNCH_CHECK("ptf_scores fold launch");
   return SAMQ_OK;
 }

@@ -124,6 +124,14 @@ SIGNATURES = {
                                         _f32, _f32, _f32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "samq_w8a8_conv_gemm_zp": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                       _f32, _f32, _f32, _f32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    # Power-of-Two Factor activations
+    "samq_layernorm_q_ptf": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _f32, _f32, _i32, _i32, _vp, _vp]),
+    "samq_i8_gemm_ptf": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _f32,
+                                _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "samq_w8a8_conv_gemm_ptf": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                       _f32, _f32, _f32, _f32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "samq_ptf_scores_workspace": (ctypes.c_size_t, [_i64, _i32]),
+    "samq_ptf_scores": (_i32, [_vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 

@@ -66,6 +66,14 @@ class QConvTranspose2d(nn.ConvTranspose2d, _QFlags):
         return F.conv_transpose2d(x, w, self.bias, self.stride, self.padding, op, self.groups, self.dilation)
 
 
+def _refuse_ptf(cfg, who: str) -> None:
+    """The prompt encoder / mask decoder mirror has no Power-of-Two Factor quantisers (``Config(ptf=True)``):
+    its ``ln=True`` QActs are not at the reference's places and the decoder engine and tail are layer-wise."""
+    if cfg is not None and cfg.INT_NORM:
+        raise NotImplementedError(f"{who}: Config(ptf=True) (INT_NORM, Power-of-Two Factor activations) is "
+                                  "supported by the image encoder only")
+
+
 def _qconvT(cfg, i, o, quant, calibrate):
     return QConvTranspose2d(i, o, kernel_size=2, stride=2, quant=quant, calibrate=calibrate, bit_type=cfg.BIT_TYPE_W,
                             calibration_mode=cfg.CALIBRATION_MODE_W, observer_str=cfg.OBSERVER_W,
@@ -82,6 +90,7 @@ class PromptEncoder(sam_decoder.PromptEncoder):
                  input_quant=False, cfg: Optional[Config] = None):
         nn.Module.__init__(self)
         cfg = cfg or sam_w8a8_config()
+        _refuse_ptf(cfg, "PromptEncoder")
         self.embed_dim = embed_dim
         self.input_image_size = input_image_size
         self.image_embedding_size = image_embedding_size
@@ -186,6 +195,7 @@ class TwoWayAttentionBlock(nn.Module):
                  activation: Type[nn.Module] = nn.ReLU, attention_downsample_rate: int = 2,
                  skip_first_layer_pe: bool = False, quant=False, calibrate=False, cfg: Optional[Config] = None):
         super().__init__()
+        _refuse_ptf(cfg, "TwoWayAttentionBlock")
         if not skip_first_layer_pe:
             self.qact_pos = _qact(cfg, quant, calibrate, permute=False)
             self.qact1 = _qact(cfg, quant, calibrate, permute=False)
@@ -230,6 +240,7 @@ class TwoWayTransformer(nn.Module):
                  activation: Type[nn.Module] = nn.ReLU, attention_downsample_rate: int = 2, quant=False,
                  calibrate=False, cfg: Optional[Config] = None):
         super().__init__()
+        _refuse_ptf(cfg, "TwoWayTransformer")
         self.depth, self.embedding_dim, self.num_heads, self.mlp_dim = depth, embedding_dim, num_heads, mlp_dim
         self.layers = nn.ModuleList([
             TwoWayAttentionBlock(embedding_dim=embedding_dim, num_heads=num_heads, mlp_dim=mlp_dim,
@@ -295,6 +306,7 @@ class MaskDecoder(nn.Module):
                  quant=False, calibrate=False, cfg: Optional[Config] = None):
         super().__init__()
         cfg = cfg or sam_w8a8_config()
+        _refuse_ptf(cfg, "MaskDecoder")
         self.cfg = cfg
         self.transformer_dim = transformer_dim
         self.transformer = transformer

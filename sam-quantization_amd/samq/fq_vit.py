@@ -28,13 +28,16 @@ non-zero: those run the zero-point engine, ``enc.engine(zero_points=True)``, on 
 codes are stored as ``code - 128`` with the zero point ``zp - 128``, so the rounding happens on
 ``q + (zp - 128)`` instead of ``q + zp``, which can differ only for quotients within about 2^-17 of
 a tie.  ``enc(img)`` picks the engine by itself; ``enc.engine()`` keeps refusing non-zero zero
-points.  Every other configuration (``ptf``: per-channel activation quantisers, ``lis``, other bit
-widths) raises ``NotImplementedError`` in quant mode.
+points.  ``Config(ptf=True)`` (the ``Config`` default) puts ``PtfObserver`` (Power-of-Two Factor: per-channel
+scales ``s0 * 2^k``, one zero point) on the QActs that feed a LayerNorm; those run the zero-point engine on
+the ``_ptf`` kernels.  ``lis`` changes nothing: the reference's ``QIntSoftmax`` returns ``F.softmax``.  Other
+bit widths raise ``NotImplementedError`` in quant mode.
 
 Every observer has a torch path for CPU tensors (the reference's ops, bit for bit) and a HIP path
 for GPU tensors: ``samq_minmax`` (minmax, ema, omse's statistics), ``samq_order_stats`` (the exact
 order statistics behind percentile's quantiles, any size, nothing copied to the host) and
-``samq_omse_scores`` (omse's 90 candidate scores in one read of the tensor).
+``samq_omse_scores`` (omse's 90 candidate scores in one read of the tensor) and ``samq_ptf_scores`` (ptf's
+four scores per channel in one read).
 
 Float and calibration forwards run the reference graph with torch ops (this is the observer
 pass, not the hot path).  In quant mode on a GPU the encoder's forward is the fused HIP engine
@@ -426,13 +429,75 @@ class OmseObserver(MinmaxObserver):
         return scale.to(dev), zero_point.to(dev)
 
 
-OBSERVERS = {"minmax": MinmaxObserver, "ema": EmaObserver, "percentile": PercentileObserver, "omse": OmseObserver}
+class PtfObserver(MinmaxObserver):
+    """``observer/ptf.py:8-74`` (Power-of-Two Factor, channel_wise): per-channel running min / max; one
+    layer-wise range gives ``scale8``, ``scale1 = scale8 / 8`` and one zero point; every channel of the
+    LAST calibration tensor then takes the scale ``scale1 * 2^k``, k in 0..3, with the smallest mean
+    squared fake-quant error (the first minimum).  Returns ``(scale [C], zero_point 0-dim)``."""
+
+    def _layer_params(self, max_val, min_val):
+        """``ptf.py:35-47`` on CPU scalars (the CPU's correctly rounded division)."""
+        qmax, qmin = self.bit_type.upper_bound, self.bit_type.lower_bound
+        max_val_t, min_val_t = max_val.max(), min_val.min()
+        scale8 = (max_val_t - min_val_t) / float(qmax - qmin)
+        scale8.clamp_(self.eps)
+        scale4 = scale8 / 2
+        scale2 = scale4 / 2
+        scale1 = scale2 / 2
+        zero_point = qmin - torch.round(min_val_t / scale8)
+        zero_point.clamp_(qmin, qmax)
+        return (scale1, scale2, scale4, scale8), zero_point
+
+    def get_quantization_params(self, inputs, *args, **kwargs):
+        qmax, qmin = self.bit_type.upper_bound, self.bit_type.lower_bound
+        if inputs.is_cuda and self.use_hip:
+            return self._params_hip(inputs)
+        scales, zero_point = self._layer_params(self.max_val, self.min_val)
+        scale_mask = torch.ones_like(self.max_val)
+        if len(inputs.shape) == 4 and self.permute:   # for Conv2d
+            inputs = inputs.permute(0, 2, 3, 1)
+        for j in range(len(scale_mask)):
+            data = inputs[..., j].unsqueeze(-1)
+            score = []
+            for s in scales:
+                data_q = ((data / s + zero_point).round().clamp(qmin, qmax) - zero_point) * s
+                score.append((data - data_q).abs().pow(2.0).mean().item())   # lp_loss(p=2, reduction="all")
+            scale_mask[j] *= 2 ** score.index(min(score))
+        return scales[0] * scale_mask, zero_point
+
+    def _params_hip(self, inputs: torch.Tensor):
+        """GPU tensors: the layer range on the host from the per-channel statistics, the 4 C scores from
+        one ``samq_ptf_scores`` read of the channel-last view (float64 sums of the f32 terms), the first
+        minimum per channel after one small read-back.  The exact sums replace torch's f32 ``.mean()``."""
+        from . import ops
+        dev = inputs.device
+        scales, zero_point = self._layer_params(self.max_val.cpu(), self.min_val.cpu())
+        x = inputs.detach()
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.float()
+        if x.dim() == 4 and self.permute:
+            x = x.permute(0, 2, 3, 1)
+        x2d = x.reshape(-1, x.shape[-1]).contiguous()
+        if x2d.shape[1] != self.max_val.numel():
+            raise ValueError(f"PtfObserver: {x2d.shape[1]} channels, statistics of {self.max_val.numel()}")
+        sums = ops.ptf_scores(x2d, float(scales[0]), float(zero_point), self.bit_type.lower_bound,
+                              self.bit_type.upper_bound).cpu().numpy()
+        pick = torch.from_numpy(sums.argmin(axis=1))   # numpy: the first minimum
+        scale_mask = torch.ones(sums.shape[0], dtype=torch.float32) * (2.0 ** pick).float()
+        return (scales[0] * scale_mask).to(dev), zero_point.to(dev)
+
+
+OBSERVERS = {"minmax": MinmaxObserver, "ema": EmaObserver, "percentile": PercentileObserver, "omse": OmseObserver,
+             "ptf": PtfObserver}
 
 
 def build_observer(observer_str, module_type, bit_type, calibration_mode, permute=True):
-    """``observer/build.py:8-19``: minmax, ema, percentile and omse (``ptf`` is not built)."""
+    """``observer/build.py:8-19``: minmax, ema, percentile, omse and ptf.  ``ptf`` is channel_wise only
+    (the pairing ``Config`` produces; the reference fails on a layer_wise one with a ``TypeError``)."""
     if observer_str not in OBSERVERS:
         raise NotImplementedError(f"observer {observer_str!r}: one of {sorted(OBSERVERS)} is supported")
+    if observer_str == "ptf" and calibration_mode != "channel_wise":
+        raise NotImplementedError("observer 'ptf': calibration_mode 'channel_wise' only")
     return OBSERVERS[observer_str](module_type, bit_type, calibration_mode, permute=permute)
 
 
@@ -720,16 +785,16 @@ class Block(nn.Module):
                  calibrate=False, cfg: Optional[Config] = None):
         super().__init__()
         self.norm1 = norm_layer(dim)
-        self.qact1 = _qact(cfg, quant, calibrate, ln=True, permute=False)
+        self.qact1 = _qact(cfg, quant, calibrate, permute=False)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, use_rel_pos=use_rel_pos,
                               rel_pos_zero_init=rel_pos_zero_init,
                               input_size=input_size if window_size == 0 else (window_size, window_size),
                               quant=quant, calibrate=calibrate, cfg=cfg)
-        self.qact2 = _qact(cfg, quant, calibrate, permute=False)
+        self.qact2 = _qact(cfg, quant, calibrate, ln=True, permute=False)   # feeds norm2
         self.norm2 = norm_layer(dim)
-        self.qact3 = _qact(cfg, quant, calibrate, ln=True, permute=False)
+        self.qact3 = _qact(cfg, quant, calibrate, permute=False)
         self.mlp = MLPBlock(dim, int(dim * mlp_ratio), act=act_layer, quant=quant, calibrate=calibrate, cfg=cfg)
-        self.qact4 = _qact(cfg, quant, calibrate, permute=False)
+        self.qact4 = _qact(cfg, quant, calibrate, ln=True, permute=False)   # feeds the next norm1 / the neck
         self.window_size = window_size
 
     def forward(self, x, last_quantizer=None):
@@ -780,7 +845,7 @@ class ImageEncoderViT(nn.Module):
         if use_abs_pos:
             self.pos_embed = nn.Parameter(torch.zeros(1, img_size // patch_size, img_size // patch_size, embed_dim))
         self.qact_pos = _qact(cfg, quant, calibrate, permute=False)
-        self.qact1 = _qact(cfg, quant, calibrate, permute=False)
+        self.qact1 = _qact(cfg, quant, calibrate, ln=True, permute=False)   # feeds the first norm1
         self.blocks = nn.ModuleList([
             Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, norm_layer=norm_layer,
                   act_layer=act_layer, use_rel_pos=use_rel_pos, rel_pos_zero_init=rel_pos_zero_init,
@@ -793,7 +858,8 @@ class ImageEncoderViT(nn.Module):
             QIntLayerNorm2D(out_chans),
             _qconv(cfg, out_chans, out_chans, 3, padding=1, bias=False, quant=quant, calibrate=calibrate),
             QIntLayerNorm2D(out_chans)])
-        self.qacts = nn.ModuleList([_qact(cfg, quant, calibrate, ln=True) for _ in range(4)])
+        # qacts[0] / qacts[2] feed the neck LayerNorms (image_encoder.py:169-190)
+        self.qacts = nn.ModuleList([_qact(cfg, quant, calibrate, ln=i in (0, 2)) for i in range(4)])
         self.global_attn_indexes = tuple(global_attn_indexes)
         self.window_size = window_size
         self._engine = None
@@ -859,11 +925,14 @@ class ImageEncoderViT(nn.Module):
         return self._engine
 
     def _needs_zero_points(self) -> bool:
-        """Any activation zero point non-zero, or unsigned activation codes."""
+        """Any activation zero point non-zero, unsigned activation codes, or a per-channel (PTF) QAct."""
         if not self.cfg.BIT_TYPE_A.signed:
             return True
         for m in self.modules():
             if isinstance(m, QAct):
+                sc = m.quantizer.scale
+                if sc is not None and sc.numel() > 1:
+                    return True
                 zp = m.quantizer.zero_point
                 if zp is not None and bool((zp != 0).any()):
                     return True
@@ -922,9 +991,10 @@ def act_quantizers(enc: nn.Module) -> dict:
 
 @torch.no_grad()
 def set_act_scales(enc: nn.Module, scales: dict, zero_points: Optional[dict] = None) -> None:
-    """Install calibrated layer-wise activation scales (what a calibrated checkpoint's
-    ``quantizer.scale`` / ``zero_point`` buffers hold) on every named QAct.  ``zero_points``: name ->
-    zero point (the reference's, in its own bit type's range); None: all zero."""
+    """Install calibrated activation scales (what a calibrated checkpoint's ``quantizer.scale`` /
+    ``zero_point`` buffers hold) on every named QAct: a scalar (layer-wise, 0-dim buffer) or a vector
+    (per channel, as ``PtfObserver`` leaves it).  ``zero_points``: name -> zero point (the reference's, in
+    its own bit type's range); None: all zero."""
     qa = act_quantizers(enc)
     missing = set(qa) - set(scales)
     if missing:
@@ -932,7 +1002,8 @@ def set_act_scales(enc: nn.Module, scales: dict, zero_points: Optional[dict] = N
     for n, m in qa.items():
         q = m.quantizer
         dev = next(enc.parameters()).device
-        sc = torch.as_tensor(scales[n], dtype=torch.float32, device=dev).reshape(())
+        sc = torch.as_tensor(scales[n], dtype=torch.float32, device=dev)
+        sc = sc.reshape(()) if sc.numel() == 1 else sc.reshape(-1).clone()
         zp = 0 if zero_points is None else int(zero_points[n])
         for name, val in (("scale", sc), ("zero_point", torch.full((), zp, dtype=torch.int64, device=dev))):
             if name in q._buffers:
@@ -997,11 +1068,48 @@ def _sz(q: QAct):
     return float(sc.reshape(-1)[0]), z
 
 
+def _szp(q: QAct):
+    """``(s0, stored zero point, exp)`` of a QAct for the zero-point engine.  Layer-wise: ``_sz`` and
+    ``exp = None``.  Per-channel (PTF, ``observer/ptf.py``): ``s0`` the smallest channel scale and ``exp``
+    a uint8 device tensor [C] with ``scale[c] = s0 * 2^exp[c]``; a scale whose ratio to ``s0`` is not
+    exactly 1, 2, 4 or 8 and a per-channel zero point are refused.  All exponents 0: ``exp = None``."""
+    sc = q.quantizer.scale
+    if sc is None:
+        raise RuntimeError("fq_vit: activation quantizer is not calibrated")
+    if sc.numel() == 1:
+        return _sz(q) + (None,)
+    bt = q.quantizer.bit_type
+    if bt.bits != 8:
+        raise NotImplementedError("W8A8 engine: 8-bit activations only")
+    zp = q.quantizer.zero_point
+    if zp is not None and zp.numel() != 1:
+        raise NotImplementedError("W8A8 engine: per-channel activation zero points are not supported")
+    z = 0 if zp is None else int(zp.reshape(-1)[0])
+    if not bt.signed:
+        z -= 128
+    if not -128 <= z <= 127:
+        raise NotImplementedError(f"W8A8 engine: zero point {z} outside the code range")
+    v = sc.detach().float().reshape(-1).cpu()
+    s0 = v.min()
+    ratio = v / s0
+    exp = torch.log2(ratio).round()
+    if not bool(((exp >= 0) & (exp <= 3) & (ratio == 2.0 ** exp) & (s0 * 2.0 ** exp == v)).all()) or float(s0) <= 0:
+        raise NotImplementedError("W8A8 engine: per-channel activation scales must be the smallest one times "
+                                  "1, 2, 4 or 8 (Power-of-Two Factors)")
+    if not bool(exp.any()):
+        return float(s0), z, None
+    return float(s0), z, exp.to(torch.uint8).to(sc.device).contiguous()
+
+
 class W8A8Engine:
     """Fused HIP forward of a calibrated fq_vit encoder (quant mode), int8 codes end to end.
 
     ``zero_points=True``: the zero-point engine -- int8 or uint8 ``BIT_TYPE_A`` and any layer-wise
-    activation zero point (omse calibration, the default ``Config``), on the ``_zp`` kernels only:
+    activation zero point (omse calibration, uint8), on the ``_zp`` kernels; with ``Config(ptf=True)``
+    (the ``Config`` default) the QActs that feed a LayerNorm carry Power-of-Two Factors (s0, zp, exp[C])
+    and the stages around them run the ``_ptf`` kernels: exponents of a GEMM's output and residual in
+    its epilogue, of a LayerNorm's input in its load, and of ``neck[0]``'s input by masked-pass replay
+    (``ops.ptf_stack_weight``).  ``lis`` changes nothing (the reference's softmax is ``F.softmax``).
     every quantiser is (scale, zp), each GEMM adds its layer's precomputed
     ``col_offset = -zp_in * sum_k W[n, k]``, the 3x3 conv pads with the zero-point code, the attention
     runs on the int8 V codes (no fp16 V copy).  One kernel chain (``row_lanes > 1`` is refused).
@@ -1023,13 +1131,13 @@ class W8A8Engine:
         cfg = enc.cfg
         self.zero_points = bool(zero_points)
         if self.zero_points:
-            if cfg.BIT_TYPE_A.bits != 8 or cfg.INT_NORM or cfg.INT_SOFTMAX:
-                raise NotImplementedError("W8A8 zero-point engine supports Config(ptf=False, lis=False) with 8-bit "
-                                          "activations (int8 or uint8)")
+            if cfg.BIT_TYPE_A.bits != 8:
+                raise NotImplementedError("W8A8 zero-point engine supports 8-bit activations (int8 or uint8)")
             self._init_zp(enc, ops)
             return
-        if not (cfg.BIT_TYPE_A.signed and cfg.BIT_TYPE_A.bits == 8) or cfg.INT_NORM or cfg.INT_SOFTMAX:
-            raise NotImplementedError("W8A8 engine supports Config(ptf=False, lis=False) with BIT_TYPE_A=int8")
+        # (INT_SOFTMAX is accepted: the reference's QIntSoftmax returns F.softmax whatever log_i_softmax is)
+        if not (cfg.BIT_TYPE_A.signed and cfg.BIT_TYPE_A.bits == 8) or cfg.INT_NORM:
+            raise NotImplementedError("W8A8 engine supports Config(ptf=False) with BIT_TYPE_A=int8")
         self.enc = enc
         # LayerNorm-q rows per wave: one (1024 workgroups for the 4096 vit_b rows instead of 512) --
         # in the W8A8 graph 1.6543 vs 1.6836 ms per image, bit-identical; the ViT-H W4A8 graph keeps
@@ -1108,15 +1216,18 @@ class W8A8Engine:
         self.pos_codes = ops.quantize_zp(enc.pos_embed.detach().float().contiguous(), *self.q_pos).reshape(
             -1, self.embed_dim)
         self.q_pe = _sz(enc.patch_embed.qact)
-        self.q_x0 = _sz(enc.qact1)
+        # the residual stream's quantisers may be PTF: (s0, zp) as for the others, the exponents beside them
+        *self.q_x0, self.e_x0 = _szp(enc.qact1)
+        self.q_x0 = tuple(self.q_x0)
         self.blocks = []
         for blk in enc.blocks:
             a = blk.attn
+            x1, x2 = _szp(blk.qact2), _szp(blk.qact4)
             q = dict(ln1=_sz(blk.qact1), qkv=_sz(a.qact1), a1=_sz(a.qact_attn1), a2=_sz(a.use_rel_pos_qact),
-                     ao=_sz(a.qact2), proj=_sz(a.qact3), x1=_sz(blk.qact2), ln2=_sz(blk.qact3), h=_sz(blk.mlp.qact1),
-                     l2=_sz(blk.mlp.qact2), x2=_sz(blk.qact4))
+                     ao=_sz(a.qact2), proj=_sz(a.qact3), x1=x1[:2], ln2=_sz(blk.qact3), h=_sz(blk.mlp.qact1),
+                     l2=_sz(blk.mlp.qact2), x2=x2[:2])
             self.blocks.append(dict(
-                window=blk.window_size, heads=a.num_heads, scale=a.scale, q=q,
+                window=blk.window_size, heads=a.num_heads, scale=a.scale, q=q, e=dict(x1=x1[2], x2=x2[2]),
                 n1=(blk.norm1.weight.detach().float().contiguous(), blk.norm1.bias.detach().float().contiguous(),
                     blk.norm1.eps),
                 n2=(blk.norm2.weight.detach().float().contiguous(), blk.norm2.bias.detach().float().contiguous(),
@@ -1125,8 +1236,11 @@ class W8A8Engine:
                 lin1=self._weight(blk.mlp.lin1, zp_in=q["ln2"][1]), lin2=self._weight(blk.mlp.lin2, zp_in=q["h"][1]),
                 relh=a.rel_pos_h.detach().float().contiguous(), relw=a.rel_pos_w.detach().float().contiguous(),
                 qkv_bias=a.qkv.bias.detach().float().contiguous() if a.qkv.bias is not None else None))
-        self.q_neck = [_sz(q) for q in enc.qacts]
-        self.neck0 = self._weight(enc.neck[0], zp_in=self.blocks[-1]["q"]["x2"][1] if self.blocks else self.q_x0[1])
+        neck = [_szp(enc.qacts[0]), _sz(enc.qacts[1]) + (None,), _szp(enc.qacts[2]), _sz(enc.qacts[3]) + (None,)]
+        self.q_neck = [t[:2] for t in neck]
+        self.e_neck = [t[2] for t in neck]
+        self.neck0 = self._weight(enc.neck[0], zp_in=self.blocks[-1]["q"]["x2"][1] if self.blocks else self.q_x0[1],
+                                  in_exp=self.blocks[-1]["e"]["x2"] if self.blocks else self.e_x0)
         self.neck2 = self._weight(enc.neck[2], tap_major=True, zp_in=self.q_neck[1][1])
         self.pad16 = torch.full((16,), self.q_neck[1][1], dtype=torch.int8, device=dev)
         self.ln_n1 = (enc.neck[1].weight.detach().float().contiguous(), enc.neck[1].bias.detach().float().contiguous(),
@@ -1134,13 +1248,34 @@ class W8A8Engine:
         self.ln_n3 = (enc.neck[3].weight.detach().float().contiguous(), enc.neck[3].bias.detach().float().contiguous(),
                       enc.neck[3].eps)
 
-    def _gemm_zp(self, a, lw, epi, q_in, q_out, q_mid=None, res=None, q_res=None, out=None):
+    def _gemm_zp(self, a, lw, epi, q_in, q_out, q_mid=None, res=None, q_res=None, out=None, e_out=None, e_res=None):
         """One ``samq_i8_gemm_zp``: input codes under q_in, output under q_out, (Q8_RES) the mid
-        quantiser q_mid and residual codes under q_res; quantisers are (scale, zero point)."""
+        quantiser q_mid and residual codes under q_res; quantisers are (scale, zero point).  PTF
+        exponents of the output (e_out), the residual (e_res) or the input (lw["passes"] > 1, the
+        replay weights of ``_weight``): ``samq_i8_gemm_ptf``."""
         mid_s, mid_z = q_mid if q_mid is not None else (0.0, 0)
         res_s, res_z = q_res if q_res is not None else (0.0, 0)
+        if e_out is not None or e_res is not None or lw.get("passes", 1) > 1:
+            return self.ops.i8_gemm_ptf(a, lw["packed"], lw["scale"], lw["n"], lw["bias"], epi, q_in[0], q_out[0], mid_s,
+                                        res_s, res, out, lw["cfg"], lw["col_offset"], mid_z, res_z, q_out[1],
+                                        out_exp=e_out, res_exp=e_res, passes=lw.get("passes", 1),
+                                        k_shift=lw.get("k_shift", (0, 0, 0)))
         return self.ops.i8_gemm_zp(a, lw["packed"], lw["scale"], lw["n"], lw["bias"], epi, q_in[0], q_out[0], mid_s,
                                    res_s, res, out, lw["cfg"], lw["col_offset"], mid_z, res_z, q_out[1])
+
+    def _ln_zp(self, x, ln, q_in, q_out, e_in, **kw):
+        """LayerNorm + quantiser on codes under q_in (PTF exponents e_in, or None)."""
+        if e_in is not None:
+            return self.ops.layernorm_q_ptf(x, ln[0], ln[1], ln[2], q_in[0], q_out[0], q_in[1], q_out[1], e_in, **kw)
+        return self.ops.layernorm_q_zp(x, ln[0], ln[1], ln[2], q_in[0], q_out[0], q_in[1], q_out[1], **kw)
+
+    def _conv_zp(self, x, mode, lw, epi, e_out=None, **kw):
+        """One implicit-GEMM conv on codes with zero points; PTF exponents of the output (e_out):
+        ``samq_w8a8_conv_gemm_ptf``, else the ``_zp`` entry with the same arguments."""
+        args = (x, mode, lw["packed"], lw["scale"], lw["n"], lw["bias"], epi)
+        if e_out is not None:
+            return self.ops.w8a8_conv_gemm_ptf(*args, col_offset=lw["col_offset"], out_exp=e_out, **kw)
+        return self.ops.w8a8_conv_gemm_zp(*args, col_offset=lw["col_offset"], **kw)
 
     @torch.no_grad()
     def _forward_zp(self, img: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
@@ -1148,9 +1283,9 @@ class W8A8Engine:
         if self.row_lanes > 1:
             raise NotImplementedError("W8A8 zero-point engine: one kernel chain only (row_lanes = 1)")
 
-        def tap(name, codes, q):
+        def tap(name, codes, q, e=None):   # (PTF quantisers: channel-last codes, scale q[0] * 2^e[c])
             if taps is not None:
-                taps[name] = (codes.float() - q[1]) * q[0]
+                taps[name] = (codes.float() - q[1]) * (q[0] if e is None else q[0] * 2.0 ** e.float())
         img = img.to(self.dev, torch.float32).contiguous()
         b, cin, hh, ww = img.shape
         p = self.patch
@@ -1158,25 +1293,26 @@ class W8A8Engine:
         c = self.embed_dim
         codes = ops.quantize_zp(img, *self.q_in)
         pw = self.patch_w
+        e_x = self.e_x0
         if p == 16 and hh == ww:
-            x = ops.w8a8_conv_gemm_zp(codes, 1, pw["packed"], pw["scale"], pw["n"], pw["bias"], ops.EPI_Q8_RES,
-                                      self.q_in[0], self.q_x0[0], mid_scale=self.q_pe[0], res_scale=self.q_pos[0],
-                                      res=self.pos_codes, rmod=gh * gw, col_offset=pw["col_offset"],
-                                      mid_zp=self.q_pe[1], res_zp=self.q_pos[1], out_zp=self.q_x0[1]).view(b * gh * gw, c)
+            x = self._conv_zp(codes, 1, pw, ops.EPI_Q8_RES, e_x, a_scale=self.q_in[0], out_scale=self.q_x0[0],
+                              mid_scale=self.q_pe[0], res_scale=self.q_pos[0], res=self.pos_codes, rmod=gh * gw,
+                              mid_zp=self.q_pe[1], res_zp=self.q_pos[1], out_zp=self.q_x0[1]).view(b * gh * gw, c)
         else:   # other patch geometries: explicit im2col
             cols = codes.view(b, cin, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(b * gh * gw, cin * p * p)
-            x = ops.i8_gemm_zp(cols.contiguous(), pw["packed"], pw["scale"], pw["n"], pw["bias"], ops.EPI_Q8_RES,
-                               self.q_in[0], self.q_x0[0], self.q_pe[0], self.q_pos[0], self.pos_codes, None, pw["cfg"],
-                               pw["col_offset"], self.q_pe[1], self.q_pos[1], self.q_x0[1], rmod=gh * gw)
+            ptf = {} if e_x is None else dict(out_exp=e_x)
+            x = (ops.i8_gemm_zp if e_x is None else ops.i8_gemm_ptf)(
+                cols.contiguous(), pw["packed"], pw["scale"], pw["n"], pw["bias"], ops.EPI_Q8_RES, self.q_in[0],
+                self.q_x0[0], self.q_pe[0], self.q_pos[0], self.pos_codes, None, pw["cfg"], pw["col_offset"],
+                self.q_pe[1], self.q_pos[1], self.q_x0[1], rmod=gh * gw, **ptf)
         q_x = self.q_x0
-        tap("qact1", x.view(b, gh, gw, c), q_x)
+        tap("qact1", x.view(b, gh, gw, c), q_x, e_x)
         xn = torch.empty_like(x)
         ao = torch.empty_like(x)
         for i, bl in enumerate(self.blocks):
             pre = f"blocks.{i}."
-            q = bl["q"]
-            g1, b1, e1 = bl["n1"]
-            ops.layernorm_q_zp(x, g1, b1, e1, q_x[0], q["ln1"][0], q_x[1], q["ln1"][1], out=xn, rows_per_wave=self.ln_rpw)
+            q, e = bl["q"], bl["e"]
+            self._ln_zp(x, bl["n1"], q_x, q["ln1"], e_x, out=xn, rows_per_wave=self.ln_rpw)
             tap(pre + "qact1", xn.view(b, gh, gw, c), q["ln1"])
             qkv = self._gemm_zp(xn, bl["qkv"], ops.EPI_Q8, q["ln1"], q["qkv"]).view(b, gh, gw, 3 * c)
             tap(pre + "attn.qact1", qkv, q["qkv"])
@@ -1184,30 +1320,28 @@ class W8A8Engine:
                                     q["qkv"][0], q["a1"][0], q["a2"][0], q["ao"][0], q["qkv"][1], q["a1"][1], q["a2"][1],
                                     q["ao"][1], out=ao.view(b, gh, gw, c))
             tap(pre + "attn.qact2", ao.view(b, gh, gw, c), q["ao"])
-            self._gemm_zp(ao, bl["proj"], ops.EPI_Q8_RES, q["ao"], q["x1"], q_mid=q["proj"], res=x, q_res=q_x, out=x)
-            tap(pre + "qact2", x.view(b, gh, gw, c), q["x1"])
-            g2, b2, e2 = bl["n2"]
-            ops.layernorm_q_zp(x, g2, b2, e2, q["x1"][0], q["ln2"][0], q["x1"][1], q["ln2"][1], out=xn,
-                               rows_per_wave=self.ln_rpw)
+            self._gemm_zp(ao, bl["proj"], ops.EPI_Q8_RES, q["ao"], q["x1"], q_mid=q["proj"], res=x, q_res=q_x, out=x,
+                          e_out=e["x1"], e_res=e_x)
+            tap(pre + "qact2", x.view(b, gh, gw, c), q["x1"], e["x1"])
+            self._ln_zp(x, bl["n2"], q["x1"], q["ln2"], e["x1"], out=xn, rows_per_wave=self.ln_rpw)
             tap(pre + "qact3", xn.view(b, gh, gw, c), q["ln2"])
             hbuf = self._gemm_zp(xn, bl["lin1"], ops.EPI_Q8_GELU, q["ln2"], q["h"])
             tap(pre + "mlp.qact1", hbuf.view(b, gh, gw, -1), q["h"])
-            self._gemm_zp(hbuf, bl["lin2"], ops.EPI_Q8_RES, q["h"], q["x2"], q_mid=q["l2"], res=x, q_res=q["x1"], out=x)
-            q_x = q["x2"]
-            tap(pre + "qact4", x.view(b, gh, gw, c), q_x)
-        sq = self.q_neck
-        y0 = self._gemm_zp(x, self.neck0, ops.EPI_Q8, q_x, sq[0])
-        y1 = ops.layernorm_q_zp(y0, self.ln_n1[0], self.ln_n1[1], self.ln_n1[2], sq[0][0], sq[1][0], sq[0][1], sq[1][1])
+            self._gemm_zp(hbuf, bl["lin2"], ops.EPI_Q8_RES, q["h"], q["x2"], q_mid=q["l2"], res=x, q_res=q["x1"], out=x,
+                          e_out=e["x2"], e_res=e["x1"])
+            q_x, e_x = q["x2"], e["x2"]
+            tap(pre + "qact4", x.view(b, gh, gw, c), q_x, e_x)
+        sq, en = self.q_neck, self.e_neck
+        y0 = self._gemm_zp(x, self.neck0, ops.EPI_Q8, q_x, sq[0], e_out=en[0])   # (the input's exponents: replay)
+        y1 = self._ln_zp(y0, self.ln_n1, sq[0], sq[1], en[0])
         oc = y1.shape[-1]
         n2 = self.neck2
-        y2 = ops.w8a8_conv_gemm_zp(y1.view(b, gh, gw, oc).contiguous(), 2, n2["packed"], n2["scale"], n2["n"], n2["bias"],
-                                   ops.EPI_Q8, sq[1][0], sq[2][0], col_offset=n2["col_offset"], out_zp=sq[2][1],
-                                   pad16=self.pad16).view(b * gh * gw, -1)
-        y3 = ops.layernorm_q_zp(y2, self.ln_n3[0], self.ln_n3[1], self.ln_n3[2], sq[2][0], sq[3][0], sq[2][1], sq[3][1],
-                                out_dtype=torch.float32)
+        y2 = self._conv_zp(y1.view(b, gh, gw, oc).contiguous(), 2, n2, ops.EPI_Q8, en[2], a_scale=sq[1][0],
+                           out_scale=sq[2][0], out_zp=sq[2][1], pad16=self.pad16).view(b * gh * gw, -1)
+        y3 = self._ln_zp(y2, self.ln_n3, sq[2], sq[3], en[2], out_dtype=torch.float32)
         return y3.view(b, gh, gw, oc).permute(0, 3, 1, 2)
 
-    def _weight(self, mod, tap_major: bool = False, zp_in: Optional[int] = None):
+    def _weight(self, mod, tap_major: bool = False, zp_in: Optional[int] = None, in_exp=None):
         """Per-output-channel symmetric int8 codes of a QLinear / QConv2d weight (the reference's
         ``quantizer(self.weight)``, layers.py:196-199) packed for the int8 MFMA GEMM.
         ``tap_major``: conv weight flattened (n, ky, kx, c), the implicit 3x3 GEMM's K order."""
@@ -1223,7 +1357,11 @@ class W8A8Engine:
         bias = None if mod.bias is None else mod.bias.detach().float().contiguous()
         lw = dict(packed=self.ops.w8_repack(codes), scale=s.contiguous(), bias=bias, n=n, k=w2.shape[1],
                   cfg=0)   # i8 GEMM tile config (0: the library's pick)
-        if zp_in is not None:   # zero-point engine: the input zero point as an int32 offset per output column
+        if in_exp is not None:   # PTF input (neck[0]): masked copies per exponent for the replay GEMM
+            stacked, lw["k_shift"], lw["col_offset"] = self.ops.ptf_stack_weight(codes, in_exp, zp_in)
+            lw["passes"] = stacked.shape[1] // w2.shape[1]
+            lw["packed"] = self.ops.w8_repack(stacked)
+        elif zp_in is not None:   # zero-point engine: the input zero point as an int32 offset per output column
             lw["col_offset"] = self.ops.w8a8_col_offset(codes, zp_in)
         return lw
 

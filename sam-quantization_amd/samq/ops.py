@@ -676,6 +676,140 @@ def w8a8_conv_gemm_zp(x: torch.Tensor, mode: int, wpacked: torch.Tensor, wscale:
     return out
 
 
+# ---- Power-of-Two Factor activations (fq_vit observer/ptf.py): a quantiser is (s0, zp, exp[C]), channel c
+# under the scale s0 * 2^exp[c]; exp a uint8 device tensor with values 0..3
+def _exp(t: Optional[torch.Tensor], n: int, what: str) -> None:
+    if t is not None:
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n, \
+            f"{what}: uint8 [{n}] on the GPU expected"
+
+
+def ptf_scores(x2d: torch.Tensor, scale1: float, zero_point: float, qmin: float, qmax: float) -> torch.Tensor:
+    """fq_vit ``PtfObserver`` scores (``samq_ptf_scores``): for every column of the contiguous f32 / f16
+    (rows, C) tensor the float64 sums over the rows of the squared fake-quant error under the scales
+    ``scale1 * (1, 2, 4, 8)`` and the zero point.  Returns a float64 (C, 4) tensor on the device."""
+    _need_cuda(x2d)
+    assert x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype in (torch.float32, torch.float16) and x2d.numel() > 0
+    rows, c = x2d.shape
+    lib = _lib.load()
+    sums = torch.empty((c, 4), dtype=torch.float64, device=x2d.device)
+    nws = lib.samq_ptf_scores_workspace(rows, c)
+    ws = torch.empty((nws + 7) // 8, dtype=torch.float64, device=x2d.device)
+    _lib.check(lib.samq_ptf_scores(_ptr(x2d), rows, c, int(x2d.dtype == torch.float16), float(scale1),
+                                   float(zero_point), float(qmin), float(qmax), _ptr(sums), _ptr(ws), nws, _stream()),
+               "ptf_scores")
+    return sums
+
+
+def layernorm_q_ptf(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, in_scale: float,
+                    out_scale: float, zp_in: int, zp_out: int, in_exp: torch.Tensor,
+                    out_dtype: torch.dtype = torch.int8, out: Optional[torch.Tensor] = None,
+                    rows_per_wave: int = 0) -> torch.Tensor:
+    """``layernorm_q_zp`` on int8 codes under a PTF quantiser: ``x = ((code - zp_in) << in_exp[c]) * in_scale``."""
+    _need_cuda(x, gamma, beta, in_exp)
+    _zp(zp_in, zp_out)
+    c = x.shape[-1]
+    assert x.dtype == torch.int8 and x.is_contiguous() and gamma.dtype == torch.float32 and beta.dtype == torch.float32
+    assert in_exp is not None, "layernorm_q_ptf: in_exp is required"
+    _exp(in_exp, c, "in_exp")
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    flags = _lib.LN_IN_I8
+    if out.dtype == torch.int8:
+        flags |= _lib.LN_OUT_I8
+    elif out.dtype == torch.float32:
+        flags |= _lib.LN_OUT_F32 | (_lib.LN_OUT_I8 if out_scale > 0 else 0)
+    flags |= rows_per_wave << 16
+    _lib.check(_lib.load().samq_layernorm_q_ptf(_ptr(x), _ptr(out), _ptr(gamma), _ptr(beta), x.numel() // c, c,
+                                                float(eps), flags, float(in_scale), float(out_scale), int(zp_in),
+                                                int(zp_out), _ptr(in_exp), _stream()), "layernorm_q_ptf")
+    return out
+
+
+def ptf_stack_weight(w: torch.Tensor, in_exp: torch.Tensor, zp_a: int):
+    """The replay operands of ``i8_gemm_ptf`` for int8 weight codes w [N, K] whose input has the per-k
+    exponents ``in_exp`` (uint8 [K], 0..3): the distinct exponents e_0 > ... > e_{P-1} = 0 (0 always
+    included), the P masked copies of w stacked along K, the shifts e_p - e_{p+1} and
+    ``col_offset[n] = -zp_a * sum_k 2^exp[k] w[n, k]`` (int64 arithmetic, checked to fit int32).
+    Returns ``(stacked [N, P * K] int8, (s0, s1, s2), col_offset int32 [N])``."""
+    _zp(zp_a)
+    n, k = w.shape
+    e = in_exp.to(w.device).to(torch.int64).reshape(-1)
+    assert e.numel() == k and int(e.min()) >= 0 and int(e.max()) <= 3, "in_exp: K values in 0..3"
+    levels = sorted(set(e.unique().tolist()) | {0}, reverse=True)
+    assert 255 * 128 * 2 ** levels[0] * k < 2 ** 31 or len(levels) == 1, "ptf replay: the int32 sums could overflow"
+    stacked = torch.cat([w * (e == lv).to(w.dtype)[None, :] for lv in levels], dim=1).contiguous()
+    shifts = [levels[p] - levels[p + 1] for p in range(len(levels) - 1)] + [0] * (4 - len(levels))
+    off = -int(zp_a) * (w.to(torch.int64) * (2 ** e)[None, :]).sum(1)
+    assert int(off.abs().max()) < 2 ** 31, "ptf replay: col_offset outside int32"
+    return stacked, tuple(shifts), off.to(torch.int32).contiguous()
+
+
+def i8_gemm_ptf(a: torch.Tensor, wpacked: torch.Tensor, wscale: torch.Tensor, n: int,
+                bias: Optional[torch.Tensor] = None, epilogue: int = EPI_Q8, a_scale: float = 1.0,
+                out_scale: float = 0.0, mid_scale: float = 0.0, res_scale: float = 0.0,
+                res: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, cfg: int = 0,
+                col_offset: Optional[torch.Tensor] = None, mid_zp: int = 0, res_zp: int = 0, out_zp: int = 0,
+                rmod: int = 0, out_exp: Optional[torch.Tensor] = None, res_exp: Optional[torch.Tensor] = None,
+                passes: int = 1, k_shift=(0, 0, 0)) -> torch.Tensor:
+    """``i8_gemm_zp`` on PTF activations (``samq_i8_gemm_ptf``): ``out_exp`` / ``res_exp`` (uint8 [N]) are the
+    output quantiser's and the residual's exponents; ``passes`` > 1 with ``k_shift``: ``wpacked`` is the
+    repack of ``ptf_stack_weight``'s stacked copies (K of the weight = passes * a.shape[-1])."""
+    _need_cuda(a, wpacked, wscale, bias, res, col_offset, out_exp, res_exp)
+    _zp(mid_zp, res_zp, out_zp)
+    assert a.dtype == torch.int8 and wscale.dtype == torch.float32
+    assert bias is None or bias.dtype == torch.float32
+    _col_offset(col_offset, n)
+    _exp(out_exp, n, "out_exp")
+    _exp(res_exp, n, "res_exp")
+    ka = a.shape[-1]
+    assert ka % 128 == 0 and 1 <= passes <= 4 and wpacked.numel() == n * ka * passes, "i8_gemm_ptf: weight size"
+    a2 = a.reshape(-1, ka)
+    out, o2 = _i8_out(a2, n, epilogue, out, tuple(a.shape[:-1]))
+    r2 = None if res is None else res.reshape(-1, n)
+    assert r2 is None or rmod == 0 or r2.shape[0] >= rmod, "i8_gemm_ptf: the residual has fewer than rmod rows"
+    assert r2 is None or rmod > 0 or r2.shape[0] >= a2.shape[0], "i8_gemm_ptf: the residual has fewer rows than A"
+    ks = tuple(int(s) for s in k_shift) + (0, 0, 0)
+    status = _lib.load().samq_i8_gemm_ptf(
+        _ptr(a2), a2.stride(0), _ptr(wpacked), _ptr(wscale), _ptr(bias), _ptr(o2), o2.stride(0), _ptr(r2),
+        0 if r2 is None else r2.stride(0), a2.shape[0], n, ka * passes, epilogue, float(a_scale), float(mid_scale),
+        float(res_scale), float(out_scale), cfg, _ptr(col_offset), int(mid_zp), int(res_zp), int(out_zp), int(rmod),
+        _ptr(out_exp), _ptr(res_exp), ka // 128, ks[0], ks[1], ks[2], _stream())
+    _lib.check(status, "i8_gemm_ptf")
+    return out
+
+
+def w8a8_conv_gemm_ptf(x: torch.Tensor, mode: int, wpacked: torch.Tensor, wscale: torch.Tensor, n: int,
+                       bias: Optional[torch.Tensor] = None, epilogue: int = EPI_Q8, a_scale: float = 1.0,
+                       out_scale: float = 0.0, mid_scale: float = 0.0, res_scale: float = 0.0,
+                       res: Optional[torch.Tensor] = None, rmod: int = 0, out: Optional[torch.Tensor] = None,
+                       col_offset: Optional[torch.Tensor] = None, mid_zp: int = 0, res_zp: int = 0, out_zp: int = 0,
+                       pad16: Optional[torch.Tensor] = None, out_exp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``w8a8_conv_gemm_zp`` with the output quantiser's exponents ``out_exp`` (``samq_w8a8_conv_gemm_ptf``)."""
+    _need_cuda(x, wpacked, wscale, bias, res, col_offset, pad16, out_exp)
+    _zp(mid_zp, res_zp, out_zp)
+    assert x.dtype == torch.int8 and x.is_contiguous() and wscale.dtype == torch.float32
+    _col_offset(col_offset, n)
+    _exp(out_exp, n, "out_exp")
+    assert pad16 is None or (pad16.dtype == torch.int8 and pad16.is_contiguous() and pad16.numel() >= 16), \
+        "pad16: 16 int8 bytes expected"
+    if mode == 1:
+        b, cin, side, _ = x.shape
+        g = side // 16
+    else:
+        b, g, _, cin = x.shape
+        side = g
+    assert res is None or res.numel() >= (rmod if rmod > 0 else b * g * g) * n, "w8a8_conv_gemm_ptf: residual too small"
+    if out is None:
+        out = torch.empty((b, g, g, n), dtype=torch.int8, device=x.device)
+    assert out.is_cuda and out.dtype == torch.int8 and out.is_contiguous() and out.numel() == b * g * g * n
+    _lib.check(_lib.load().samq_w8a8_conv_gemm_ptf(
+        _ptr(x), mode, b, cin, side, _ptr(wpacked), _ptr(wscale), _ptr(bias), _ptr(out), _ptr(res), rmod, n, epilogue,
+        float(a_scale), float(mid_scale), float(res_scale), float(out_scale), _ptr(col_offset), int(mid_zp),
+        int(res_zp), int(out_zp), _ptr(pad16), _ptr(out_exp), _stream()), "w8a8_conv_gemm_ptf")
+    return out
+
+
 def w4a8_gemm(a, wpacked3, wscale, qzeros, n, bias=None, epilogue=EPI_BIAS, a_scale=1.0, out_scale=0.0,
               out=None, groupsize=-1, cfg=0, rowsum=None, rowsum_out=None):
     """GPTQ int4 weights (repacked layout 3) x int8 activation codes (cfg 0 = library pick).

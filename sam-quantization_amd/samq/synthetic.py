@@ -75,16 +75,17 @@ def flops_per_image(enc) -> dict:
 
 def random_fq_encoder(name: str = "vit_b", device="cuda", seed: int = 0, img_size: int = 1024,
                       calib_images: int = 1, depth: int | None = None, quant_method: str = "minmax",
-                      global_attn_indexes=None, act_bit_type: str = "int8"):
+                      global_attn_indexes=None, act_bit_type: str = "int8", ptf: bool = False, lis: bool = False):
     """fq_vit W8A8 encoder with random weights (same init as ``random_quant_encoder``), calibrated
     on ``calib_images`` seeded standard-normal images (the reference's calibration sequence, run on
     ``device``) and switched to quant mode.  ``quant_method``: the activation observer (minmax, ema,
-    percentile, omse -- ``Config(False, False, quant_method)``) and ``act_bit_type`` its activation bit
+    percentile, omse -- ``Config(ptf, lis, quant_method)``; ``ptf=True`` puts Power-of-Two Factor quantisers
+    on the QActs that feed a LayerNorm, which run on the zero-point engine) and ``act_bit_type`` its activation bit
     type ("int8", or "uint8" as in the default ``Config``); an omse-calibrated or uint8 encoder has
     non-zero zero points and runs on the zero-point engine (``enc.engine(zero_points=True)``).
     ``global_attn_indexes``: as ``build_fq_image_encoder`` (None: the named model's)."""
     from .fq_vit import BIT_TYPE_DICT, Config, build_fq_image_encoder
-    cfg = Config(False, False, quant_method)
+    cfg = Config(ptf, lis, quant_method)
     cfg.BIT_TYPE_A = BIT_TYPE_DICT[act_bit_type]
     enc = build_fq_image_encoder(name, img_size=img_size, depth=depth, cfg=cfg,
                                  global_attn_indexes=global_attn_indexes)
