@@ -323,6 +323,25 @@ size_t samq_ptf_scores_workspace(int64_t rows, int C);
 int samq_ptf_scores(const void* x, int64_t rows, int C, int in_f16, float scale1, float zero_point, float qmin,
                     float qmax, double* sums, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* The blocked column loop of GPTQ.fasterquant (reference gptq.py:97-146, blocksize 128) in one launch.
+ *   W      f32 (rows, K) row-major.  In: the weights, dead columns already 0 and act-order already applied;
+ *          out: the fake-quantised weights scale * (code - zero).
+ *   U      f32 (K, K) row-major: the upper Cholesky factor of the inverse damped Hessian (the reference's
+ *          "Hinv"); only its upper triangle is read.
+ *   codes  uint8 (rows, K): the integer codes 0..maxq; may be NULL.
+ *   scale, zero  f32 (rows, G), G = 1 (groupsize -1) or K / groupsize.
+ * Per column c: q = clamp(rint(w / scale) + zero, 0, maxq), fake = scale * (q - zero), err = (w - fake) / U[c, c];
+ * the later columns of the block lose err * U[c, j] at once, the columns behind the block lose
+ * Err1 @ U[i1:i2, i2:] before the next block.  Group parameters (Quantizer.find_params: min / max widened to
+ * include 0, all-zero slice -> (-1, 1), scale = (max - min) / maxq, zero = rint(-min / scale)) are taken at a
+ * group's first column from the reference's OUTER W: columns of the current block as of the block's start,
+ * later columns as of the last trailing update; groupsize -1 takes them from the whole input row.  fp32
+ * throughout, every operation rounded as torch's separate ops round it, IEEE divisions, rint half-even.
+ * K % 128 == 0, groupsize in {-1, 32, 64, 128, 256} and K % groupsize == 0 (else SAMQ_ERR_UNSUPPORTED);
+ * maxq 3..255; W and U 16-byte aligned.  The kernel needs no workspace: workspace is not read (NULL, 0). */
+int samq_gptq_quant(float* W, const float* U, uint8_t* codes, float* scale, float* zero, int rows, int K,
+                    int groupsize, int maxq, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* samq_rel_attention_q8_rows on codes with zero points: qkv codes (s_qkv, zp_qkv), the two score
  * quantisers (s_a1, zp_a1) / (s_a2, zp_a2), output codes (s_out, zp_out).  q.k is
  * sum_d (q - zp_qkv)(k - zp_qkv), exact in int32; the rel-pos terms take (q - zp_qkv) s_qkv; the

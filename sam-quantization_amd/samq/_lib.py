@@ -132,6 +132,8 @@ SIGNATURES = {
                                        _f32, _f32, _f32, _f32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "samq_ptf_scores_workspace": (ctypes.c_size_t, [_i64, _i32]),
     "samq_ptf_scores": (_i32, [_vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, ctypes.c_size_t, _vp]),
+    # GPTQ producer
+    "samq_gptq_quant": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, ctypes.c_size_t, _vp]),
 }
 
 

@@ -3,7 +3,8 @@
 * ``Quantizer``      -- asymmetric per-channel min/max parameters (reference ``gptq.py:200-299``,
                         ``perchannel=True, sym=False``; ``mse`` grid search not used by the SAM scripts);
 * ``GPTQ``           -- Hessian accumulation + the blockwise optimal-brain-quantiser update
-                        (reference ``gptq.py:15-171``), in fp32 torch on the layer's device;
+                        (reference ``gptq.py:15-171``) on the layer's device: Hessian and Cholesky in
+                        fp32 torch, the blocked column loop in one HIP launch (``ops.gptq_quant``);
 * ``sam_sequential`` -- the reference's block-by-block calibration of the SAM encoder
                         (``gptq4sam.py:280-431``, true-sequential groups qkv / proj / lin1+lin2);
 * ``pack_linear``    -- bit-identical to the reference's packing (``gptq4sam.py:434-497``),
@@ -20,6 +21,7 @@ from pathlib import Path
 import torch
 import torch.nn as nn
 
+from . import ops
 from .quant_linear import QuantLinear, make_quant
 
 
@@ -28,9 +30,10 @@ class Quantizer:
         self.maxq = 2 ** bits - 1
 
     def find_params(self, w: torch.Tensor):
-        """Per-row ``scale, zero`` (fp32) for ``w`` (rows, cols)."""
-        w = w.float()
-        zero_t = torch.zeros(w.shape[0], device=w.device)
+        """Per-row ``scale, zero`` for ``w`` (rows, cols), in fp32 (float64 weights: in float64)."""
+        if w.dtype != torch.float64:
+            w = w.float()
+        zero_t = torch.zeros(w.shape[0], device=w.device, dtype=w.dtype)
         xmin = torch.minimum(w.min(1).values, zero_t)
         xmax = torch.maximum(w.max(1).values, zero_t)
         both0 = (xmin == 0) & (xmax == 0)
@@ -54,7 +57,8 @@ class GPTQ:
     column inside blocks of ``blocksize``, pushing each column's scaled error onto the columns
     not yet quantised; group parameters are taken from the error-updated weights at each group
     start.  The layer's weight is replaced by the fake-quantised one; returns ``(scale, zero)``
-    of shape (rows, groups).
+    of shape (rows, groups).  ``column_loop`` is that loop as torch ops (any float dtype, any device),
+    ``ops.gptq_quant`` the same loop as one HIP kernel.
     """
 
     def __init__(self, layer: nn.Module, bits: int = 4):
@@ -74,12 +78,14 @@ class GPTQ:
         self.H += x @ x.t()
 
     @torch.no_grad()
-    def fasterquant(self, blocksize: int = 128, percdamp: float = 0.01, groupsize: int = -1,
-                    actorder: bool = False):
-        W = self.layer.weight.data.clone().reshape(self.rows, -1).float()
-        qz = self.quantizer
-        scale, zero = qz.find_params(W)
-        H = self.H
+    def prepare(self, percdamp: float = 0.01, actorder: bool = False, dtype: torch.dtype = torch.float32):
+        """Everything of ``fasterquant`` in front of the column loop, in ``dtype``: the per-row parameters
+        of the whole weight, dead columns, act-order, damping and the two Cholesky calls.  Consumes H.
+        Returns ``(W, U, perm, scale, zero, dead)``: the (permuted) weights, the upper factor "Hinv", the
+        act-order permutation or None, the whole-row parameters and the dead-column mask."""
+        W = self.layer.weight.data.clone().reshape(self.rows, -1).to(dtype)
+        scale, zero = self.quantizer.find_params(W)
+        H = self.H.to(dtype)
         self.H = None
         dead = torch.diagonal(H) == 0
         H[dead, dead] = 1.0
@@ -91,35 +97,66 @@ class GPTQ:
         idx = torch.arange(self.columns, device=self.dev)
         H[idx, idx] += percdamp * torch.mean(torch.diagonal(H))
         L = torch.linalg.cholesky(H)
-        Hinv = torch.linalg.cholesky(torch.cholesky_inverse(L), upper=True)
-        Q = torch.zeros_like(W)
-        scales, zeros = [], []
-        for i1 in range(0, self.columns, blocksize):
-            i2 = min(i1 + blocksize, self.columns)
-            W1 = W[:, i1:i2].clone()
-            Err1 = torch.zeros_like(W1)
-            Hinv1 = Hinv[i1:i2, i1:i2]
-            for i in range(i2 - i1):
-                col = i1 + i
-                if groupsize != -1 and col % groupsize == 0:
-                    # the reference reads the OUTER W here: columns of the current block as of the
-                    # block start, later columns as of the last block update (gptq.py:113-117)
-                    scale, zero = qz.find_params(W[:, col:col + groupsize])
-                    scales.append(scale)
-                    zeros.append(zero)
-                w = W1[:, i]
-                q = qz.quantize(w, scale, zero)
-                Q[:, col] = q
-                err = (w - q) / Hinv1[i, i]
-                W1[:, i:] -= err[:, None] * Hinv1[i, i:][None, :]
-                Err1[:, i] = err
-            W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]
+        U = torch.linalg.cholesky(torch.cholesky_inverse(L), upper=True)
+        return W, U, perm, scale, zero, dead
+
+    @torch.no_grad()
+    def fasterquant(self, blocksize: int = 128, percdamp: float = 0.01, groupsize: int = -1,
+                    actorder: bool = False, backend: str = "auto", dtype: torch.dtype = torch.float32):
+        """``backend="auto"``: the column loop runs in the HIP kernel (``ops.gptq_quant``) when the weight
+        is on the GPU in fp32, ``blocksize == 128`` and the shape is one the kernel is built for
+        (K % 128 == 0, groupsize -1 / 32 / 64 / 128 / 256 dividing K), else in torch;
+        ``backend="torch"`` forces the torch loop, which works in ``dtype``."""
+        assert backend in ("auto", "torch")
+        W, U, perm, scale, zero, dead = self.prepare(percdamp, actorder, dtype)
+        qz = self.quantizer
+        # groupsize -1 takes its parameters from the row BEFORE the dead columns are zeroed: the kernel
+        # sees only the zeroed weight, so a layer with dead columns stays on the torch loop there
+        if (backend == "auto" and W.is_cuda and dtype == torch.float32 and blocksize == 128
+                and ops.gptq_supported(self.columns, groupsize, qz.maxq)
+                and not (groupsize == -1 and bool(dead.any()))):
+            Q, scales, zeros, _ = ops.gptq_quant(W, U, groupsize, qz.maxq)
+        else:
+            Q, scales, zeros = column_loop(W, U, qz, blocksize, groupsize, scale, zero)
         if perm is not None:
             Q = Q[:, torch.argsort(perm)]
         self.layer.weight.data = Q.reshape(self.layer.weight.shape).to(self.layer.weight.dtype)
-        if not scales:
-            scales, zeros = [scale], [zero]
-        return torch.stack(scales, 1), torch.stack(zeros, 1)
+        return scales, zeros
+
+
+def column_loop(W: torch.Tensor, Hinv: torch.Tensor, qz: Quantizer, blocksize: int = 128, groupsize: int = -1,
+                scale=None, zero=None):
+    """The blocked column loop of ``fasterquant`` as torch ops, in ``W``'s dtype and on its device
+    (``W`` is consumed).  ``scale, zero``: the whole-row parameters for ``groupsize == -1`` (default:
+    ``find_params(W)``).  Returns ``(Q, scales (rows, G), zeros (rows, G))``."""
+    columns = W.shape[1]
+    if scale is None:
+        scale, zero = qz.find_params(W)
+    Q = torch.zeros_like(W)
+    scales, zeros = [], []
+    for i1 in range(0, columns, blocksize):
+        i2 = min(i1 + blocksize, columns)
+        W1 = W[:, i1:i2].clone()
+        Err1 = torch.zeros_like(W1)
+        Hinv1 = Hinv[i1:i2, i1:i2]
+        for i in range(i2 - i1):
+            col = i1 + i
+            if groupsize != -1 and col % groupsize == 0:
+                # the reference reads the OUTER W here: columns of the current block as of the
+                # block start, later columns as of the last block update (gptq.py:113-117)
+                scale, zero = qz.find_params(W[:, col:col + groupsize])
+                scales.append(scale)
+                zeros.append(zero)
+            w = W1[:, i]
+            q = qz.quantize(w, scale, zero)
+            Q[:, col] = q
+            err = (w - q) / Hinv1[i, i]
+            W1[:, i:] -= err[:, None] * Hinv1[i, i:][None, :]
+            Err1[:, i] = err
+        W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:]
+    if not scales:
+        scales, zeros = [scale], [zero]
+    return Q, torch.stack(scales, 1), torch.stack(zeros, 1)
 
 
 @torch.no_grad()

@@ -701,6 +701,37 @@ def ptf_scores(x2d: torch.Tensor, scale1: float, zero_point: float, qmin: float,
     return sums
 
 
+# ----------------------------------------------------------------------------- GPTQ producer
+GPTQ_GROUPSIZES = (-1, 32, 64, 128, 256)
+
+
+def gptq_supported(k: int, groupsize: int, maxq: int) -> bool:
+    """The shapes ``samq_gptq_quant`` is built for (the guards of the C entry)."""
+    return (k > 0 and k % 128 == 0 and groupsize in GPTQ_GROUPSIZES and (groupsize == -1 or k % groupsize == 0)
+            and 3 <= maxq <= 255)
+
+
+def gptq_quant(W: torch.Tensor, U: torch.Tensor, groupsize: int, maxq: int):
+    """The blocked column loop of ``GPTQ.fasterquant`` (blocksize 128) in one launch (``samq_gptq_quant``).
+    ``W`` f32 (rows, K): the weights with dead columns zeroed and act-order applied (not modified);
+    ``U`` f32 (K, K): the upper Cholesky factor of the inverse damped Hessian.  Returns ``(Q, scale, zero,
+    codes)``: the fake-quantised weights (rows, K) f32, the group parameters (rows, G) f32 and the integer
+    codes (rows, K) uint8.  Unsupported K / groupsize: NotImplementedError."""
+    _need_cuda(W, U)
+    assert W.dim() == 2 and W.dtype == torch.float32 and U.dtype == torch.float32
+    rows, k = W.shape
+    assert tuple(U.shape) == (k, k), "gptq_quant: U must be (K, K)"
+    q = W.contiguous().clone()
+    U = U.contiguous()
+    g = 1 if groupsize == -1 else max(k // max(int(groupsize), 1), 1)
+    scale = torch.empty((rows, g), dtype=torch.float32, device=W.device)
+    zero = torch.empty((rows, g), dtype=torch.float32, device=W.device)
+    codes = torch.empty((rows, k), dtype=torch.uint8, device=W.device)
+    _lib.check(_lib.load().samq_gptq_quant(_ptr(q), _ptr(U), _ptr(codes), _ptr(scale), _ptr(zero), rows, k,
+                                           int(groupsize), int(maxq), None, 0, _stream()), "gptq_quant")
+    return q, scale, zero, codes
+
+
 def layernorm_q_ptf(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, in_scale: float,
                     out_scale: float, zp_in: int, zp_out: int, in_exp: torch.Tensor,
                     out_dtype: torch.dtype = torch.int8, out: Optional[torch.Tensor] = None,
