@@ -628,6 +628,29 @@ int samq_conv1x1_f32(const float* x, const void* weight, void* out, int64_t M, i
 int samq_conv3x3_nhwc(const void* x, const void* weight, void* out, int B, int G, int Cin, int N,
                       hipStream_t stream);
 
+/* ---------------------------------------------------------------- mask post-processing */
+
+/* Sam.postprocess_masks (segment_anything/modeling/sam.py:133-162) + `> mask_threshold` +
+ * calculate_stability_score + batched_mask_to_box (segment_anything/utils/amg.py) in one pass over the
+ * low-res logits, as automatic_mask_generator.py _process_batch needs them.
+ *   low    (N, lh, lw) contiguous, f32 (f16 with low_f16); lh == lw, img_size == 4 lh.
+ *   v      = bilinear(crop(bilinear(low, img_size x img_size), ih x iw), H x W), both resizes with
+ *            align_corners = False under torch's fp32 coordinate rule (scale = float(in) / float(out),
+ *            src = max(scale (dst + 0.5) - 0.5, 0), i0 = int(src), i1 = i0 + (i0 < in - 1)); the second one
+ *            clamps at the crop's edge.  v is never written to memory.
+ *   mask   uint8 (N, H, W), 1 where v > thr; NULL: statistics only.
+ *   stats  int32 (N, 8): #(v > thr + off), #(v > thr - off), #(v > thr), then the inclusive box x0, y0, x1,
+ *          y1 of the mask (0, 0, 0, 0 when it is empty), then 0.  Integer sums and extremes of
+ *          per-workgroup rows, folded in a fixed order: the same on every run.
+ * Two launches on `stream` (the kernel, then one wave per mask folding the workgroups' rows held in the
+ * caller's workspace, samq_mask_postprocess_workspace(...) bytes, 4-byte aligned; 0 for sizes the entry
+ * rejects); no atomics, no memset, no host round trip.  SAMQ_ERR_INVALID: lh != lw, img_size != 4 lh,
+ * a size < 1, ih or iw > img_size, H * W >= 2^31, off < 0. */
+size_t samq_mask_postprocess_workspace(int N, int lh, int lw, int img_size, int ih, int iw, int H, int W);
+int samq_mask_postprocess(const void* low, int low_f16, int N, int lh, int lw, int img_size, int ih, int iw,
+                          int H, int W, float thr, float off, uint8_t* mask, int32_t* stats, void* workspace,
+                          size_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

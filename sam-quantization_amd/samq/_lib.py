@@ -134,6 +134,10 @@ SIGNATURES = {
     "samq_ptf_scores": (_i32, [_vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, ctypes.c_size_t, _vp]),
     # GPTQ producer
     "samq_gptq_quant": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, ctypes.c_size_t, _vp]),
+    # mask post-processing
+    "samq_mask_postprocess_workspace": (ctypes.c_size_t, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "samq_mask_postprocess": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp,
+                                     _vp, ctypes.c_size_t, _vp]),
 }
 
 

@@ -1100,3 +1100,33 @@ def upscale1_masks_q8(x: torch.Tensor, w_hi: torch.Tensor, w_lo: torch.Tensor, b
                                                   cout, nm, float(s_in), float(s3), float(s4), float(s_q1), _stream()),
                "upscale1_masks_q8")
     return masks
+
+
+# ----------------------------------------------------------------------------- mask post-processing
+def mask_postprocess(low: torch.Tensor, img_size: int, input_size, original_size, threshold: float = 0.0,
+                     offset: float = 1.0, masks: bool = True):
+    """``postprocess_masks(low, img_size, input_size, original_size) > threshold`` with the counts of
+    ``calculate_stability_score`` and the boxes of ``batched_mask_to_box`` in one pass over the low-res
+    logits (``samq_mask_postprocess``); no fp32 image of the padded-input or the original size is written.
+    ``low`` f32 / f16 (N, lh, lw) or (B, C, lh, lw), square, ``img_size == 4 * lh``.  Returns ``(mask, stats)``:
+    ``mask`` bool (..., H, W) (``None`` with ``masks=False``), ``stats`` int32 (..., 8) = ``[inter, union, area,
+    x0, y0, x1, y1, 0]`` with inter / union / area the pixel counts above ``threshold + offset`` /
+    ``threshold - offset`` / ``threshold`` and the inclusive xyxy box of the mask (zeros when it is empty)."""
+    _need_cuda(low)
+    assert low.dim() in (3, 4) and low.dtype in (torch.float32, torch.float16), \
+        "mask_postprocess: low must be f32 / f16 (N, lh, lw) or (B, C, lh, lw)"
+    lead = tuple(low.shape[:-2])
+    lh, lw = int(low.shape[-2]), int(low.shape[-1])
+    (ih, iw), (h, w) = (int(v) for v in input_size), (int(v) for v in original_size)
+    x = low.reshape(-1, lh, lw).contiguous()
+    n = x.shape[0]
+    lib = _lib.load()
+    # 0 for sizes the C entry rejects (it checks them before anything is launched): no mask is allocated then
+    nws = lib.samq_mask_postprocess_workspace(n, lh, lw, int(img_size), ih, iw, h, w)
+    stats = torch.empty((n, 8), dtype=torch.int32, device=low.device)
+    ws = torch.empty(max(nws // 4, 1), dtype=torch.int32, device=low.device)
+    out = torch.empty((n, h, w), dtype=torch.bool, device=low.device) if masks and (nws or n == 0) else None
+    _lib.check(lib.samq_mask_postprocess(_ptr(x), int(x.dtype == torch.float16), n, lh, lw, int(img_size), ih, iw,
+                                         h, w, float(threshold), float(offset), _ptr(out), _ptr(stats), _ptr(ws),
+                                         nws, _stream()), "mask_postprocess")
+    return (out.view(lead + (h, w)) if masks else None), stats.view(lead + (8,))

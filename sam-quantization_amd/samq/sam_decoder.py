@@ -386,6 +386,33 @@ class SamPredictor:
             masks = masks > self.model.mask_threshold
         return masks, iou, low
 
+    @torch.no_grad()
+    def predict_torch_scored(self, point_coords, point_labels, boxes=None, mask_input=None, multimask_output=True,
+                             stability_score_offset=1.0, return_masks=True):
+        """``predict_torch`` with what ``SamAutomaticMaskGenerator._process_batch``
+        (``automatic_mask_generator.py``) derives from the full-size logits: the same prompt-encoder and
+        mask-decoder calls, then ONE pass of the HIP kernel behind ``ops.mask_postprocess`` over the low-res
+        logits instead of ``postprocess_masks``, the threshold, ``calculate_stability_score`` and
+        ``batched_mask_to_box``.  Returns a dict: ``masks`` bool (B, C, H, W) (``None`` without
+        ``return_masks``), ``iou_predictions``, ``low_res_logits``, ``stability_score`` f32 (B, C), ``boxes``
+        int32 xyxy (B, C, 4), ``areas`` int32 (B, C).  GPU only."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
+        if not self.features.is_cuda:
+            raise NotImplementedError("predict_torch_scored runs the HIP mask post-processing kernel: GPU only")
+        from . import ops
+        points = (point_coords, point_labels) if point_coords is not None else None
+        sparse, dense = self.model.prompt_encoder(points=points, boxes=boxes, masks=mask_input)
+        low, iou = self.model.mask_decoder(self.features, self.model.prompt_encoder.get_dense_pe(), sparse, dense,
+                                           multimask_output)
+        logits = low if low.dtype in (torch.float16, torch.float32) else low.float()
+        masks, stats = ops.mask_postprocess(logits, self.model.image_encoder.img_size, self.input_size,
+                                            self.original_size, self.model.mask_threshold, stability_score_offset,
+                                            masks=return_masks)
+        return {"masks": masks, "iou_predictions": iou, "low_res_logits": low,
+                "stability_score": stats[..., 0].float() / stats[..., 1].float(),
+                "boxes": stats[..., 3:7], "areas": stats[..., 2]}
+
     def predict(self, point_coords=None, point_labels=None, box=None, mask_input=None, multimask_output=True,
                 return_logits=False):
         if not self.is_image_set:
