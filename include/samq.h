@@ -651,6 +651,45 @@ int samq_mask_postprocess(const void* low, int low_f16, int N, int lh, int lw, i
                           int H, int W, float thr, float off, uint8_t* mask, int32_t* stats, void* workspace,
                           size_t workspace_bytes, hipStream_t stream);
 
+/* ---------------------------------------------------------------- automatic mask generator */
+
+/* Uncompressed COCO run-length encoding of selected masks on a canvas:
+ * mask_to_rle_pytorch(uncrop_masks(masks[sel], crop_box, H, W)) (segment_anything/utils/amg.py) with no
+ * padded copy, no transposed copy and no index tensor.
+ *   masks   uint8 / bool (N, h, w) contiguous, non-zero = set (what samq_mask_postprocess writes).
+ *   sel     int32 (n_sel) indices into N, any order, repeats allowed; an index outside [0, N) reads nothing
+ *           and encodes an empty canvas.
+ *   x0, y0, H, W   the mask occupies [y0, y0 + h) x [x0, x0 + w) of an all-zero H x W canvas, H * W < 2^31.
+ *   offsets int64 (n_sel + 1), counts int32 (offsets[n_sel]): row i = counts[offsets[i] .. offsets[i + 1]) holds
+ *           the run lengths of canvas i flattened in Fortran order (p = X * H + Y), the first a run of zeros
+ *           (0 when pixel (0, 0) is set); every row sums to H * W.
+ * samq_mask_rle_count: the count pass (transitions per column and 64-row band, int32 [mask][column][band] in
+ * the workspace), its exclusive scan in place and `offsets`: three launches.  The caller reads offsets[n_sel]
+ * (the one host round trip of the whole encoding), allocates `counts` and `positions` (scratch) of that many
+ * int32 each, and calls samq_mask_rle_write with the SAME masks, sel, placement, offsets and workspace: the
+ * flat position of every transition goes to `positions`, then the run lengths to `counts`: two launches.
+ * No atomics; the result is the same on every run.  samq_mask_rle_workspace: bytes of the 4-byte aligned
+ * workspace, 0 for arguments the entries reject.  SAMQ_ERR_INVALID: a size < 1, the mask not inside the
+ * canvas, H * W >= 2^31, a null or misaligned pointer, a short workspace, counts == positions. */
+size_t samq_mask_rle_workspace(int N, int n_sel, int h, int w, int x0, int y0, int H, int W);
+int samq_mask_rle_count(const uint8_t* masks, int N, const int32_t* sel, int n_sel, int h, int w, int x0, int y0,
+                        int H, int W, int64_t* offsets, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int samq_mask_rle_write(const uint8_t* masks, int N, const int32_t* sel, int n_sel, int h, int w, int x0, int y0,
+                        int H, int W, const int64_t* offsets, void* workspace, size_t workspace_bytes,
+                        int32_t* positions, int32_t* counts, int64_t total, hipStream_t stream);
+
+/* Greedy box NMS with torchvision.ops.nms's fp32 arithmetic.  boxes f32 xyxy (n, 4), 16-byte aligned, ALREADY
+ * in rank order (descending score, equal scores by ascending index); order int32 (n): the original index of
+ * each rank.  Box j is dropped when a kept box i of higher rank has
+ * inter / (area_i + area_j - inter) > thr (true IEEE division; NaN compares false: the box stays).
+ *   keep    int32 (n): the original indices of the kept boxes, in rank order; n_keep int32 (1), on the device.
+ * Two launches: the upper-triangular 64 x 64 tiles of the suppression bit matrix into the workspace
+ * (samq_box_nms_workspace(n) = n * ceil(n / 64) * 8 bytes, 8-byte aligned; 0 for n <= 0 or n > 32768), then
+ * the sweep as one workgroup.  n > 32768: SAMQ_ERR_UNSUPPORTED. */
+size_t samq_box_nms_workspace(int n);
+int samq_box_nms(const float* boxes, const int32_t* order, int n, float thr, int32_t* keep, int32_t* n_keep,
+                 void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,14 @@ SIGNATURES = {
     "samq_mask_postprocess_workspace": (ctypes.c_size_t, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "samq_mask_postprocess": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp,
                                      _vp, ctypes.c_size_t, _vp]),
+    # automatic mask generator: column-major RLE, box NMS
+    "samq_mask_rle_workspace": (ctypes.c_size_t, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "samq_mask_rle_count": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
+                                   ctypes.c_size_t, _vp]),
+    "samq_mask_rle_write": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
+                                   ctypes.c_size_t, _vp, _vp, _i64, _vp]),
+    "samq_box_nms_workspace": (ctypes.c_size_t, [_i32]),
+    "samq_box_nms": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 

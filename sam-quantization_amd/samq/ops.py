@@ -1130,3 +1130,67 @@ def mask_postprocess(low: torch.Tensor, img_size: int, input_size, original_size
                                          h, w, float(threshold), float(offset), _ptr(out), _ptr(stats), _ptr(ws),
                                          nws, _stream()), "mask_postprocess")
     return (out.view(lead + (h, w)) if masks else None), stats.view(lead + (8,))
+
+
+# ----------------------------------------------------------------------------- automatic mask generator
+def mask_rle(masks: torch.Tensor, sel: Optional[torch.Tensor] = None, crop_box=None, orig_size=None):
+    """Uncompressed COCO RLE of ``uncrop_masks(masks[sel], crop_box, H, W)`` (``samq_mask_rle_*``): no padded copy,
+    no transposed copy, no index tensor, ONE host read (``offsets[-1]``, to size ``counts``) however many masks.
+    ``masks`` bool / uint8 (N, h, w) contiguous; ``sel`` integer indices into N (any order, repeats allowed;
+    ``None``: all); ``crop_box`` xyxy ``[x0, y0, x1, y1]`` with ``x1 - x0 == w`` and ``y1 - y0 == h`` placed on an
+    ``orig_size = (H, W)`` canvas (both ``None``: the mask is the canvas).  Returns device tensors ``(offsets,
+    counts)``: int64 (n_sel + 1) and int32 (offsets[-1]); row ``i`` = ``counts[offsets[i]:offsets[i + 1]]`` is the
+    run lengths of canvas ``i`` in Fortran order, starting with a run of zeros."""
+    _need_cuda(masks, sel)
+    assert masks.dim() == 3 and masks.dtype in (torch.bool, torch.uint8), \
+        "mask_rle: masks must be bool / uint8 (N, h, w)"
+    assert masks.is_contiguous(), "mask_rle: masks must be contiguous"
+    n, h, w = (int(v) for v in masks.shape)
+    if sel is None:
+        sel = torch.arange(n, dtype=torch.int32, device=masks.device)
+    assert sel.dim() == 1 and not sel.is_floating_point() and sel.dtype != torch.bool, \
+        "mask_rle: sel must be integer indices"
+    sel = sel.to(torch.int32).contiguous()
+    n_sel = int(sel.numel())
+    x0, y0 = (int(crop_box[0]), int(crop_box[1])) if crop_box is not None else (0, 0)
+    if crop_box is not None:
+        assert int(crop_box[2]) - x0 == w and int(crop_box[3]) - y0 == h, "mask_rle: crop_box must have the masks' size"
+    hh, ww = (int(v) for v in orig_size) if orig_size is not None else (y0 + h, x0 + w)
+    offsets = torch.zeros(n_sel + 1, dtype=torch.int64, device=masks.device)
+    if n_sel == 0:
+        return offsets, torch.empty(0, dtype=torch.int32, device=masks.device)
+    lib = _lib.load()
+    nws = lib.samq_mask_rle_workspace(n, n_sel, h, w, x0, y0, hh, ww)
+    ws = torch.empty(max(nws // 4, 1), dtype=torch.int32, device=masks.device)
+    place = (n, _ptr(sel), n_sel, h, w, x0, y0, hh, ww)
+    _lib.check(lib.samq_mask_rle_count(_ptr(masks), *place, _ptr(offsets), _ptr(ws), nws, _stream()), "mask_rle")
+    total = int(offsets[-1])       # the one sync
+    counts = torch.empty(total, dtype=torch.int32, device=masks.device)
+    positions = torch.empty(total, dtype=torch.int32, device=masks.device)
+    _lib.check(lib.samq_mask_rle_write(_ptr(masks), *place, _ptr(offsets), _ptr(ws), nws, _ptr(positions),
+                                       _ptr(counts), total, _stream()), "mask_rle")
+    return offsets, counts
+
+
+def box_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torch.Tensor:
+    """``torchvision.ops.nms(boxes, scores, iou_threshold)`` (``samq_box_nms``): boxes (n, 4) xyxy, compared in fp32
+    with torchvision's arithmetic; rank by descending score, equal scores by ascending index.  The suppression
+    matrix and the greedy sweep stay on the device; the one host read is the number of kept boxes.  Returns the
+    kept indices, int64, in rank order."""
+    _need_cuda(boxes, scores)
+    assert boxes.dim() == 2 and boxes.shape[1] == 4, "box_nms: boxes must be (n, 4)"
+    n = int(boxes.shape[0])
+    assert scores.dim() == 1 and scores.numel() == n, "box_nms: one score per box"
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=boxes.device)
+    order = torch.sort(scores, stable=True, descending=True).indices
+    ranked = boxes.float()[order].contiguous()
+    order = order.to(torch.int32)
+    lib = _lib.load()
+    nws = lib.samq_box_nms_workspace(n)
+    ws = torch.empty(max(nws // 8, 1), dtype=torch.int64, device=boxes.device)
+    keep = torch.empty(n, dtype=torch.int32, device=boxes.device)
+    n_keep = torch.empty(1, dtype=torch.int32, device=boxes.device)
+    _lib.check(lib.samq_box_nms(_ptr(ranked), _ptr(order), n, float(iou_threshold), _ptr(keep), _ptr(n_keep),
+                                _ptr(ws), nws, _stream()), "box_nms")
+    return keep[:int(n_keep)].long()

@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""The automatic mask generator's two irregular steps per call: ``ops.mask_rle`` and ``ops.box_nms`` against
+plain-torch compositions written for this tool.
+
+    python tools/bench_amg.py [--reps 7] [--out amg.jsonl]
+
+RLE: 192 blob-like masks (smooth low-res logits: seeded 8 x 8 noise upsampled to 256 x 256, through
+``ops.mask_postprocess``) at 1024 x 1024, 683 x 1024 and 1200 x 1800, of which about 10 %, 50 % and 100 % are
+selected.  The torch composition is the upstream recipe without its pad: the masks are the whole canvas here
+(no crop), where the upstream uncrop step hands them on as they are, so it starts at the permute to Fortran
+order, then xor of neighbours, ``nonzero``, and per mask a boolean split and a host transfer.  NMS: n = 192, 3072 and 12288 boxes
+clustered around 40 centres, seeded scores, threshold 0.7, against a greedy loop on the device (one row of IoUs
+per kept box).  The two paths alternate ``--reps`` times after a warm-up of each; a timed run is ``inner``
+back-to-back calls on the host clock between device synchronisations, ``inner`` chosen so a run lasts about 20 ms
+or more.  One JSON line per point: medians per call in ms, min / max of the runs, whether the two paths agree
+and, for the RLE, the HBM bound of two reads of the selected masks at 8 TB/s and the HIP path's share of it.
+"""
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "sam-quantization_amd"))
+
+import torch  # noqa: E402
+
+HBM_BYTES_PER_S = 8e12
+
+
+def torch_rle(masks, sel):
+    """mask_to_rle_pytorch on masks[sel]: a list of run-length lists."""
+    m = masks[sel]
+    b, h, w = m.shape
+    t = m.permute(0, 2, 1).flatten(1)
+    idx = (t[:, 1:] ^ t[:, :-1]).nonzero()
+    first = t[:, 0].cpu().tolist()
+    out = []
+    for i in range(b):
+        cur = idx[idx[:, 0] == i, 1] + 1
+        ends = torch.cat([cur.new_zeros(1), cur, cur.new_full((1,), h * w)])
+        runs = (ends[1:] - ends[:-1]).cpu().tolist()
+        out.append(([0] if first[i] else []) + runs)
+    return out
+
+
+def torch_nms(boxes, scores, thr):
+    order = torch.sort(scores, stable=True, descending=True).indices
+    b = boxes[order]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    dead = torch.zeros(len(b), dtype=torch.bool, device=b.device)
+    keep = []
+    for i in range(len(b)):
+        if dead[i]:
+            continue
+        keep.append(i)
+        w = (torch.minimum(b[i, 2], b[i + 1:, 2]) - torch.maximum(b[i, 0], b[i + 1:, 0])).clamp(min=0)
+        h = (torch.minimum(b[i, 3], b[i + 1:, 3]) - torch.maximum(b[i, 1], b[i + 1:, 1])).clamp(min=0)
+        dead[i + 1:] |= w * h / (area[i] + area[i + 1:] - w * h) > thr
+    return order[torch.tensor(keep, device=b.device)]
+
+
+def timed(fn, inner):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(inner):
+        out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / inner * 1e3, out
+
+
+def compare(paths, reps):
+    inner, t, out = {}, {k: [] for k in paths}, {}
+    for name, fn in paths.items():
+        timed(fn, 1)
+        inner[name] = max(1, min(200, int(20.0 / max(timed(fn, 1)[0], 1e-3))))
+    for _ in range(reps):
+        for name, fn in paths.items():
+            dt, out[name] = timed(fn, inner[name])
+            t[name].append(dt)
+    res = {"inner": inner}
+    for k, v in t.items():
+        res[f"{k}_ms"] = round(statistics.median(v), 4)
+        res[f"{k}_min_max_ms"] = [round(min(v), 4), round(max(v), 4)]
+    res["speedup"] = round(res["torch_ms"] / res["hip_ms"], 2)
+    return res, out
+
+
+def rle_point(orig, frac, reps, dev):
+    from samq import ops
+    from samq.sam_decoder import ResizeLongestSide
+    g = torch.Generator(device="cpu").manual_seed(orig[0] + orig[1])
+    low = torch.nn.functional.interpolate(3 * torch.randn((192, 1, 8, 8), generator=g) - 1.5, (256, 256),
+                                          mode="bicubic")[:, 0].contiguous().to(dev)
+    inp = ResizeLongestSide.get_preprocess_shape(orig[0], orig[1], 1024)
+    masks, _ = ops.mask_postprocess(low, 1024, inp, orig)
+    n_sel = max(1, round(192 * frac))
+    sel = torch.randperm(192, generator=g)[:n_sel].to(dev)
+    res, out = compare({"torch": lambda: torch_rle(masks, sel), "hip": lambda: ops.mask_rle(masks, sel)}, reps)
+    offsets, counts = (v.cpu() for v in out["hip"])
+    same = [counts[offsets[i]:offsets[i + 1]].tolist() for i in range(n_sel)] == out["torch"]
+    bound_ms = 2 * n_sel * orig[0] * orig[1] / HBM_BYTES_PER_S * 1e3
+    return dict(op="mask_rle", size=list(orig), n_sel=n_sel, runs=int(offsets[-1]), **res,
+                hbm_bound_ms=round(bound_ms, 5), hip_share_of_hbm_bound=round(bound_ms / res["hip_ms"], 4), equal=same)
+
+
+def nms_point(n, reps, dev):
+    from samq import ops
+    g = torch.Generator(device="cpu").manual_seed(n)
+    centre = 1024 * torch.rand((40, 2), generator=g)
+    c = centre[torch.randint(0, 40, (n,), generator=g)] + 30 * torch.randn((n, 2), generator=g)
+    half = 20 + 100 * torch.rand((n, 2), generator=g)
+    boxes = torch.cat([c - half, c + half], 1).round().to(dev)
+    scores = torch.rand(n, generator=g).to(dev)
+    res, out = compare({"torch": lambda: torch_nms(boxes, scores, 0.7), "hip": lambda: ops.box_nms(boxes, scores, 0.7)},
+                       reps)
+    return dict(op="box_nms", n=n, kept=int(out["hip"].numel()), **res, equal=bool(torch.equal(out["hip"], out["torch"])))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_amg: no GPU visible; timings are taken on the GPU only")
+    dev = torch.device("cuda:0")
+    name = torch.cuda.get_device_name(0)
+    points = [lambda o=o, f=f: rle_point(o, f, a.reps, dev) for o in ((1024, 1024), (683, 1024), (1200, 1800))
+              for f in (0.1, 0.5, 1.0)] + [lambda n=n: nms_point(n, a.reps, dev) for n in (192, 3072, 12288)]
+    for p in points:
+        line = json.dumps(dict(p(), reps=a.reps, device=name))
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
