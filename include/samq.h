@@ -690,6 +690,35 @@ size_t samq_box_nms_workspace(int n);
 int samq_box_nms(const float* boxes, const int32_t* order, int n, float thr, int32_t* keep, int32_t* n_keep,
                  void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* Small-region removal on the run-length encoding: per mask remove_small_regions(mask, min_area, "holes") then
+ * (.., "islands") (segment_anything/utils/amg.py, cv2.connectedComponentsWithStats with 8-connectivity), with no
+ * mask image: connected components over the runs cut at column boundaries.
+ *   offsets int64 (n + 1), counts int32 (total_in = offsets[n]): CSR rows as samq_mask_rle_* writes them, on an
+ *           H x W canvas, H * W < 2^31; min_area >= 1.
+ *   Holes (components of zeros, the outer background included) below min_area are filled; then islands below
+ *   min_area are dropped, keeping the largest if all are small -- on an exact tie the one that holds the
+ *   earliest pixel in column-major order (OpenCV: the lowest label, an implementation detail).
+ *   new_offsets int64 (n + 1), new_counts int32 (new_offsets[n]): the cleaned rows, same format; a row that
+ *           nothing changed equals its input.
+ *   stats   int32 (n, 8): x0, y0, x1, y1 (inclusive xyxy box, zeros for an empty mask, as batched_mask_to_box),
+ *           area, unchanged (0 also when the only island is small and stays: the reference's flag), segments,
+ *           transitions.
+ * samq_rle_regions_label: one workgroup per mask labels and counts, one wave writes new_offsets: two launches.
+ * The caller reads new_offsets[n] (the one host round trip), allocates new_counts and calls
+ * samq_rle_regions_write with the SAME offsets, sizes and workspace: one launch.  Integer atomics with an
+ * order-independent outcome only; the result is the same on every run.  A row that breaks the format (runs
+ * not summing to H * W, offsets outside [0, total_in]) is clamped and gives a wrong row, never an access
+ * outside the buffers.  samq_rle_regions_workspace: bytes of the 4-byte aligned workspace, 0 for arguments
+ * the entries reject.  SAMQ_ERR_INVALID: n < 0, a size < 1, H * W >= 2^31, min_area < 1, total_in < n, a null
+ * or misaligned pointer, a short workspace; SAMQ_ERR_UNSUPPORTED: total_in + W >= 2^31. */
+size_t samq_rle_regions_workspace(int n, int64_t total_in, int H, int W);
+int samq_rle_regions_label(const int64_t* offsets, const int32_t* counts, int n, int64_t total_in, int H, int W,
+                           int min_area, int64_t* new_offsets, int32_t* stats, void* workspace,
+                           size_t workspace_bytes, hipStream_t stream);
+int samq_rle_regions_write(const int64_t* offsets, int n, int64_t total_in, int H, int W, const int64_t* new_offsets,
+                           void* workspace, size_t workspace_bytes, int32_t* new_counts, int64_t new_total,
+                           hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,10 @@ SIGNATURES = {
                                    ctypes.c_size_t, _vp, _vp, _i64, _vp]),
     "samq_box_nms_workspace": (ctypes.c_size_t, [_i32]),
     "samq_box_nms": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    # automatic mask generator: small-region removal on the RLE
+    "samq_rle_regions_workspace": (ctypes.c_size_t, [_i32, _i64, _i32, _i32]),
+    "samq_rle_regions_label": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "samq_rle_regions_write": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, ctypes.c_size_t, _vp, _i64, _vp]),
 }
 
 

@@ -5,13 +5,17 @@ the defaults and the output records of ``segment_anything/automatic_mask_generat
   masks, stability scores, boxes, areas), the three filters as one boolean tensor on the device, and
   ``ops.mask_rle`` of the surviving masks straight onto the full-image canvas (no ``uncrop_masks`` copy);
 * per crop ``ops.box_nms`` on the predicted IoUs, across crops ``ops.box_nms`` on ``1 / crop area``;
+* with ``min_mask_region_area > 0`` ``ops.rle_remove_small_regions`` on the run lengths of the survivors (no mask is
+  decoded) and a third ``ops.box_nms`` that prefers the masks it left untouched (``postprocess_small_regions``);
 * host lists are built once per crop from the CSR tensors (one device-to-host copy per field), not once per mask.
 
 Host round trips, none of which grows with the number of masks.  Per batch: two reads (the size of the
 selection from ``nonzero``, the RLE total inside ``ops.mask_rle``) and two small uploads (the crop / image
 boxes of the edge filter, the batch's points).  Per crop: two reads (the kept count inside ``ops.box_nms``, the
 kept rows' RLE total), two small uploads (the crop's shift and box) and the six copies of the result.  Per image
-with more than one crop: the kept count of the NMS across crops and its index list.
+with more than one crop: the kept count of the NMS across crops and its index list.  Per image with
+``min_mask_region_area > 0``: the cleaned rows' RLE total, the kept count of that NMS, one small upload (the
+survivors' row indices) and the copies of the result.
 GPU only, with any ``Sam`` the predictor accepts (GPTQ, fq_sam or float).
 """
 from __future__ import annotations
@@ -76,6 +80,19 @@ def _xywh(box: List[int]) -> List[int]:
     return [box[0], box[1], box[2] - box[0], box[3] - box[1]]
 
 
+def _gather_rows(lens: torch.Tensor, counts: torch.Tensor, rows: torch.Tensor, total: Optional[int]):
+    """Rows ``rows`` of a CSR batch (row lengths ``lens``, entries ``counts``) as a new CSR batch ``(offsets,
+    counts)``, on the device.  ``total``: the number of entries gathered, read from the device when ``None``."""
+    starts = torch.cumsum(lens, 0) - lens
+    klen = lens[rows]
+    koff = torch.cat([klen.new_zeros(1), torch.cumsum(klen, 0)])
+    if total is None:
+        total = int(koff[-1])
+    src = torch.repeat_interleave(starts[rows] - koff[:-1], klen, output_size=total) \
+        + torch.arange(total, device=counts.device)
+    return koff, counts[src]
+
+
 class SamAutomaticMaskGenerator:
     def __init__(self, model, points_per_side: Optional[int] = 32, points_per_batch: int = 64,
                  pred_iou_thresh: float = 0.88, stability_score_thresh: float = 0.95,
@@ -112,7 +129,11 @@ class SamAutomaticMaskGenerator:
     def generate(self, image: np.ndarray) -> List[Dict[str, Any]]:
         """Mask records for an HWC uint8 image: ``segmentation``, ``area``, ``bbox`` (xywh), ``predicted_iou``,
         ``point_coords``, ``stability_score``, ``crop_box`` (xywh)."""
-        return self.records(self.candidates(image), image.shape[:2])
+        cand = self.candidates(image)
+        if self.min_mask_region_area > 0:
+            cand = self.postprocess_small_regions(cand, image.shape[:2], self.min_mask_region_area,
+                                                  max(self.box_nms_thresh, self.crop_nms_thresh))
+        return self.records(cand, image.shape[:2])
 
     @torch.no_grad()
     def candidates(self, image: np.ndarray):
@@ -150,6 +171,36 @@ class SamAutomaticMaskGenerator:
                         "stability_score": c["stab_l"][r], "crop_box": _xywh(c["crop_box"])})
         return out
 
+    @staticmethod
+    @torch.no_grad()
+    def postprocess_small_regions(candidates, orig_size, min_area: int, nms_thresh: float):
+        """Holes and islands below ``min_area`` removed from every surviving mask, then a box NMS that ranks the
+        masks this left untouched first (score 1 against 0), as the reference's method of this name.  Takes what
+        ``candidates(image)`` returns and gives back the same structure for ``records``: one entry per crop, all
+        sharing the arrays of the cleaned survivors (row ``k`` is ``where[k]``), and the kept ``(crop, row)``
+        pairs in the NMS's order.  Host reads: the cleaned rows' RLE total and the kept count of the NMS."""
+        crops, where = candidates
+        if not where:
+            return candidates
+        dev = crops[0]["boxes"].device
+        # the survivors' rows out of the crops' device CSR copies, in `where` order; their total from the host copy
+        base = np.concatenate([[0], np.cumsum([len(c["boxes_l"]) for c in crops])])
+        rows = torch.tensor([int(base[ci]) + r for ci, r in where], device=dev)
+        total = sum(int(crops[ci]["offsets"][r + 1] - crops[ci]["offsets"][r]) for ci, r in where)
+        offsets, counts = _gather_rows(torch.cat([c["offsets_d"].diff() for c in crops]),
+                                       torch.cat([c["counts_d"] for c in crops]), rows, total)
+        offsets, counts, new_boxes, _, unchanged = ops.rle_remove_small_regions(offsets, counts, orig_size, min_area)
+        keep = ops.box_nms(new_boxes.float(), unchanged.float(), nms_thresh)
+        # a row that nothing changed equals its input, so the cleaned rows serve for every mask; the box is
+        # replaced for the changed ones only
+        boxes = torch.where(unchanged[:, None], torch.cat([c["boxes"] for c in crops])[rows], new_boxes.long())
+        merged = {"boxes": boxes, "boxes_l": boxes.tolist(), "offsets": offsets.cpu().numpy(),
+                  "counts": counts.cpu().numpy(), "offsets_d": offsets, "counts_d": counts}
+        for field in ("iou_l", "stab_l", "points_l"):
+            merged[field] = [crops[ci][field][r] for ci, r in where]
+        out = [{**merged, "crop_box": c["crop_box"], "crop_box_t": c["crop_box_t"]} for c in crops]
+        return out, [(where[k][0], k) for k in keep.tolist()]
+
     def _process_crop(self, image, crop_box, layer, orig_size):
         x0, y0, x1, y1 = crop_box
         crop = image[y0:y1, x0:x1, :]
@@ -173,19 +224,15 @@ class SamAutomaticMaskGenerator:
         lens = torch.cat([d["offsets"].diff() for d in batches])
         counts = torch.cat([d["counts"] for d in batches])
         keep = ops.box_nms(boxes.float(), iou, self.box_nms_thresh)
-        # the kept rows' run lengths, gathered on the device in keep order
-        starts = torch.cumsum(lens, 0) - lens
-        klen = lens[keep]
-        koff = torch.cat([klen.new_zeros(1), torch.cumsum(klen, 0)])
-        total = int(koff[-1])           # the crop's second host read (the first is box_nms's kept count)
-        src = torch.repeat_interleave(starts[keep] - koff[:-1], klen, output_size=total) \
-            + torch.arange(total, device=dev)
+        # the kept rows' run lengths, gathered on the device in keep order; the total is the crop's second host
+        # read (the first is box_nms's kept count)
+        koff, kcounts = _gather_rows(lens, counts, keep, None)
         # to the host once per crop, one copy per field
         full = boxes[keep] + shift
         return {"crop_box": list(crop_box), "crop_box_t": torch.tensor([crop_box], device=dev),
                 "boxes": full, "boxes_l": full.tolist(), "iou_l": iou[keep].tolist(), "stab_l": stab[keep].tolist(),
                 "points_l": (pts[keep] + shift[:2]).tolist(), "offsets": koff.cpu().numpy(),
-                "counts": counts[src].cpu().numpy()}
+                "counts": kcounts.cpu().numpy(), "offsets_d": koff, "counts_d": kcounts}
 
     def _process_batch(self, points, crop_size, crop_box, orig_size):
         """One batch of points of one crop -> the device tensors of its surviving candidates (or ``None``)."""

@@ -1194,3 +1194,39 @@ def box_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> 
     _lib.check(lib.samq_box_nms(_ptr(ranked), _ptr(order), n, float(iou_threshold), _ptr(keep), _ptr(n_keep),
                                 _ptr(ws), nws, _stream()), "box_nms")
     return keep[:int(n_keep)].long()
+
+
+def rle_remove_small_regions(offsets: torch.Tensor, counts: torch.Tensor, size, min_area: int):
+    """``remove_small_regions(mask, min_area, "holes")`` then ``(.., "islands")`` of every mask of a CSR RLE batch
+    (``samq_rle_regions_*``): connected components with 8-connectivity over the runs cut at column boundaries, no
+    mask image, ONE host read (the new ``offsets[-1]``, to size the new ``counts``) however many masks.
+    ``offsets`` int64 (n + 1) and ``counts`` int32 (offsets[-1]) as ``mask_rle`` returns them, on a ``size = (H,
+    W)`` canvas; ``min_area >= 1``.  Holes (the outer background included) below ``min_area`` are filled, then
+    islands below it dropped; if all islands are small the largest stays, on an exact tie the one holding the
+    earliest pixel in column-major order.  Returns device tensors ``(offsets, counts, boxes, areas, unchanged)``:
+    the cleaned rows in the same format (an untouched row equals its input), int32 (n, 4) inclusive xyxy boxes
+    (zeros for an empty mask), int32 (n) areas and bool (n) flags, ``False`` also for a mask whose only island is
+    small and therefore stays (the reference's flag)."""
+    _need_cuda(offsets, counts)
+    assert offsets.dim() == 1 and offsets.dtype == torch.int64 and offsets.numel() >= 1, \
+        "rle_remove_small_regions: offsets must be int64 (n + 1)"
+    assert counts.dim() == 1 and counts.dtype == torch.int32, "rle_remove_small_regions: counts must be int32"
+    offsets, counts = offsets.contiguous(), counts.contiguous()
+    n, total_in = int(offsets.numel()) - 1, int(counts.numel())
+    hh, ww = (int(v) for v in size)
+    dev = offsets.device
+    new_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    stats = torch.empty((n, 8), dtype=torch.int32, device=dev)
+    if n == 0:
+        return new_offsets, torch.empty(0, dtype=torch.int32, device=dev), stats[:, :4], stats[:, 4], stats[:, 5] != 0
+    lib = _lib.load()
+    nws = lib.samq_rle_regions_workspace(n, total_in, hh, ww)
+    ws = torch.empty(max(nws // 4, 1), dtype=torch.int32, device=dev)
+    _lib.check(lib.samq_rle_regions_label(_ptr(offsets), _ptr(counts), n, total_in, hh, ww, int(min_area),
+                                          _ptr(new_offsets), _ptr(stats), _ptr(ws), nws, _stream()),
+               "rle_remove_small_regions")
+    total = int(new_offsets[-1])       # the one sync
+    new_counts = torch.empty(total, dtype=torch.int32, device=dev)
+    _lib.check(lib.samq_rle_regions_write(_ptr(offsets), n, total_in, hh, ww, _ptr(new_offsets), _ptr(ws), nws,
+                                          _ptr(new_counts), total, _stream()), "rle_remove_small_regions")
+    return new_offsets, new_counts, stats[:, :4], stats[:, 4], stats[:, 5] != 0

@@ -14,6 +14,11 @@ per kept box).  The two paths alternate ``--reps`` times after a warm-up of each
 back-to-back calls on the host clock between device synchronisations, ``inner`` chosen so a run lasts about 20 ms
 or more.  One JSON line per point: medians per call in ms, min / max of the runs, whether the two paths agree
 and, for the RLE, the HBM bound of two reads of the selected masks at 8 TB/s and the HIP path's share of it.
+
+Small regions (``--only regions``): ``ops.rle_remove_small_regions`` with ``min_area`` 100 on the run lengths of all
+192 blob masks at the three sizes, with the segments per mask, against the upstream host composition per mask
+(decode, connected components twice, box, re-encode) where the host has OpenCV or, failing that,
+``scipy.ndimage``; the ``host`` field says which, ``null`` and no comparison if neither.
 """
 import argparse
 import json
@@ -84,7 +89,9 @@ def compare(paths, reps):
     for k, v in t.items():
         res[f"{k}_ms"] = round(statistics.median(v), 4)
         res[f"{k}_min_max_ms"] = [round(min(v), 4), round(max(v), 4)]
-    res["speedup"] = round(res["torch_ms"] / res["hip_ms"], 2)
+    other = next((k for k in paths if k != "hip"), None)
+    if other is not None:
+        res["speedup"] = round(res[f"{other}_ms"] / res["hip_ms"], 2)
     return res, out
 
 
@@ -119,10 +126,85 @@ def nms_point(n, reps, dev):
     return dict(op="box_nms", n=n, kept=int(out["hip"].numel()), **res, equal=bool(torch.equal(out["hip"], out["torch"])))
 
 
+def host_labeller():
+    """(name, label function) of the host's connected components: OpenCV as the upstream step uses it, else
+    scipy.ndimage with the 8-neighbour structure, else ``(None, None)``.  label(mask) -> (labels, areas incl. 0)."""
+    try:
+        import cv2
+        return "cv2", lambda m: (lambda r: (r[1], r[2][:, -1]))(cv2.connectedComponentsWithStats(m.astype("uint8"), 8))
+    except ImportError:
+        pass
+    try:
+        import numpy as np
+        from scipy import ndimage
+        return "scipy.ndimage", lambda m: (lambda lab: (lab, np.bincount(lab.ravel())))(
+            ndimage.label(m, structure=np.ones((3, 3), dtype=int))[0])
+    except ImportError:
+        return None, None
+
+
+def host_regions(offsets, counts, size, min_area, label):
+    """The upstream host composition per mask: decode, holes, islands, box, re-encode of the changed ones."""
+    import numpy as np
+    from samq.automatic_mask_generator import rle_to_mask
+    offsets, counts = offsets.cpu().numpy(), counts.cpu().numpy()
+    rows, boxes, same = [], [], []
+    for i in range(len(offsets) - 1):
+        row = counts[offsets[i]:offsets[i + 1]]
+        mask = rle_to_mask({"size": list(size), "counts": row})
+        changed = False
+        for holes in (True, False):
+            lab, areas = label(mask ^ holes)
+            small = [k for k in range(1, len(areas)) if areas[k] < min_area]
+            if not small:
+                continue
+            changed = True
+            fill = [0] + small
+            if not holes:
+                fill = [k for k in range(len(areas)) if k not in fill] or [int(np.argmax(areas[1:])) + 1]
+            mask = np.isin(lab, fill)
+        ys, xs = np.nonzero(mask)
+        boxes.append([xs.min(), ys.min(), xs.max(), ys.max()] if len(xs) else [0, 0, 0, 0])
+        same.append(not changed)
+        if changed:
+            flat = mask.flatten(order="F")
+            ends = np.concatenate([[0], np.flatnonzero(flat[1:] != flat[:-1]) + 1, [flat.size]])
+            row = np.concatenate([[0] if flat[0] else [], np.diff(ends)]).astype(np.int32)
+        rows.append(row)
+    return rows, boxes, same
+
+
+def regions_point(orig, reps, dev, min_area=100):
+    from samq import ops
+    from samq.sam_decoder import ResizeLongestSide
+    g = torch.Generator(device="cpu").manual_seed(orig[0] + orig[1])
+    low = torch.nn.functional.interpolate(3 * torch.randn((192, 1, 8, 8), generator=g) - 1.5, (256, 256),
+                                          mode="bicubic")[:, 0].contiguous().to(dev)
+    masks, _ = ops.mask_postprocess(low, 1024, ResizeLongestSide.get_preprocess_shape(orig[0], orig[1], 1024), orig)
+    offsets, counts = ops.mask_rle(masks)
+    segments = (masks[:, 1:] != masks[:, :-1]).sum((1, 2)) + orig[1]
+    name, label = host_labeller()
+    paths = {"hip": lambda: ops.rle_remove_small_regions(offsets, counts, orig, min_area)}
+    if label is not None:
+        paths["host"] = lambda: host_regions(offsets, counts, orig, min_area, label)
+    res, out = compare(paths, reps)
+    o, c, boxes, _, same = (v.cpu() for v in out["hip"])
+    rec = dict(op="rle_remove_small_regions", size=list(orig), n=192, min_area=min_area, runs=int(offsets[-1]),
+               segments_per_mask=round(float(segments.float().mean()), 1), segments_max=int(segments.max()),
+               changed=int((~same).sum()), **res, host=name)
+    if label is not None:
+        rows, hboxes, hsame = out["host"]
+        # a tie between the largest of all-small islands may go to another island on the host: see DESIGN.md
+        rec["equal"] = (all(c[o[i]:o[i + 1]].tolist() == rows[i].tolist() for i in range(192))
+                        and boxes.tolist() == [[int(v) for v in b] for b in hboxes] and same.tolist() == hsame)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default="")
+    ap.add_argument("--only", default="", choices=["", "mask_rle", "box_nms", "regions"])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_amg: no GPU visible; timings are taken on the GPU only")
@@ -130,6 +212,9 @@ def main():
     name = torch.cuda.get_device_name(0)
     points = [lambda o=o, f=f: rle_point(o, f, a.reps, dev) for o in ((1024, 1024), (683, 1024), (1200, 1800))
               for f in (0.1, 0.5, 1.0)] + [lambda n=n: nms_point(n, a.reps, dev) for n in (192, 3072, 12288)]
+    points += [lambda o=o: regions_point(o, a.reps, dev) for o in ((1024, 1024), (683, 1024), (1200, 1800))]
+    if a.only:
+        points = [p for p, op in zip(points, ["mask_rle"] * 9 + ["box_nms"] * 3 + ["regions"] * 3) if op == a.only]
     for p in points:
         line = json.dumps(dict(p(), reps=a.reps, device=name))
         print(line, flush=True)
