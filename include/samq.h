@@ -719,6 +719,33 @@ int samq_rle_regions_write(const int64_t* offsets, int n, int64_t total_in, int 
                            void* workspace, size_t workspace_bytes, int32_t* new_counts, int64_t new_total,
                            hipStream_t stream);
 
+/* ---------------------------------------------------------------- click simulator */
+
+/* The next click of the RITM evaluation protocol (inference/clicker.py Clicker._get_next_click with padding)
+ * and the counts of get_iou (inference/utils.py), per mask of a batch, in exact integer arithmetic.
+ *   pred    uint8 / bool (n, H, W), non-zero = predicted; gt int8 (n, H, W): 1 object, 0 background,
+ *           ignore_label = counts for neither.  1 <= H, W <= 4096, n < 65536.
+ *   clicked int32 (n, K, 2): the (y, x) pixels already clicked, K <= 64 (NULL with K == 0); a slot with y < 0
+ *           is unused, a pixel outside the image matches nothing.
+ *   fn = gt == 1 & !pred & gt != ignore, fp = gt != 1 & pred & gt != ignore.  d2 of a map at (y, x): the squared
+ *   Euclidean distance to the nearest zero pixel of the map padded by a one-pixel ring of zeros (what
+ *   cv2.distanceTransform(pad(map, 1), DIST_L2, 0)[1:-1, 1:-1] returns, squared).  With d2 zeroed at the clicked
+ *   pixels, fn_max / fp_max are the maxima of the two maps; the click is positive iff fn_max > fp_max and goes
+ *   to the first pixel in row-major order that attains the chosen maximum ((0, 0) when that maximum is 0).
+ *   out     int32 (n, 8): is_positive, y, x, fn_max, fp_max (squared distances), inter = #(pred & gt == 1 &
+ *           !ignore), union = #((pred | gt == 1) & !ignore), 0.
+ *   d2      NULL, or int32 (n, 2, H, W): the fn and the fp map, clicked pixels NOT zeroed.
+ * Four launches on `stream` (column bits and counts, column distances, row search, one wave per mask folding
+ * the workgroups' rows held in the workspace); no atomics, no memset, no float: the same on every run.
+ * samq_next_click_workspace: bytes of the 8-byte aligned workspace (a multiple of 8), 0 for sizes the entry
+ * rejects.
+ * SAMQ_ERR_INVALID: n outside 1 .. 65535 (n == 0 is a no-op), H or W outside 1 .. 4096, K outside 0 .. 64, a
+ * null or misaligned pointer, a short workspace. */
+size_t samq_next_click_workspace(int n, int H, int W);
+int samq_next_click(const uint8_t* pred, const int8_t* gt, const int32_t* clicked, int K, int n, int H, int W,
+                    int ignore_label, int32_t* out, int32_t* d2, void* workspace, size_t workspace_bytes,
+                    hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

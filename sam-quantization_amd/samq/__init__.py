@@ -26,12 +26,14 @@ from . import fq_sam  # noqa: F401
 from .fq_sam import build_fq_sam  # noqa: F401
 from .sam_decoder import ResizeLongestSide, SamPredictor, mask_iou  # noqa: F401
 from .automatic_mask_generator import SamAutomaticMaskGenerator  # noqa: F401
+from .clicker import Click, Clicker  # noqa: F401
+from .click_eval import compute_noc_metric, evaluate_sample  # noqa: F401
 
 __all__ = [
     "load_quant", "autotune_warmup", "QuantLinear", "make_quant", "matmul4", "triton_matmul4",
     "QuantAttention", "make_quant_attn", "ImageEncoderViT", "Sam", "sam_model_registry",
     "make_act_quant", "calibrate_act_quant", "fq_vit", "fq_sam", "build_fq_sam", "SamPredictor", "ResizeLongestSide", "mask_iou",
-    "SamAutomaticMaskGenerator",
+    "SamAutomaticMaskGenerator", "Click", "Clicker", "evaluate_sample", "compute_noc_metric",
 ]
 
 

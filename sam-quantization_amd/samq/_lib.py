@@ -150,6 +150,9 @@ SIGNATURES = {
     "samq_rle_regions_workspace": (ctypes.c_size_t, [_i32, _i64, _i32, _i32]),
     "samq_rle_regions_label": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "samq_rle_regions_write": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, ctypes.c_size_t, _vp, _i64, _vp]),
+    # click simulator: exact distance transform, next click, IoU counts
+    "samq_next_click_workspace": (ctypes.c_size_t, [_i32, _i32, _i32]),
+    "samq_next_click": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 

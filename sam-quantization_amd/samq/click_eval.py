@@ -15,7 +15,7 @@ golden) and ground-truth masks ``(B, 1, H, W)`` with 1 = object, 0 = background 
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -115,3 +115,60 @@ def synthetic_gt_masks(n: int, size: int = 1024, seed: int = 0, ignore_band: int
         m[np.abs(r - 1.0) < band] = -1.0
         masks[i, 0] = m
     return torch.from_numpy(masks)
+
+
+@torch.no_grad()
+def evaluate_sample(image, gt_mask, predictor, max_iou_thr, min_clicks=1, max_clicks=20, callback=None):
+    """The RITM evaluation loop for one sample (reference ``inference/evaluation.py::evaluate_sample``) on a
+    ``SamPredictor``: ``set_image`` once, then per click ``predict_torch`` with ``multimask_output=False``, the
+    accumulated clicks as point prompts and, from the second click on, the previous low-res logits as the mask
+    prompt.  Every click is the first deepest pixel of the larger error region of the previous prediction
+    (``samq.clicker.Clicker`` on ``ops.next_click``); the ONE kernel call per prediction yields that prediction's
+    IoU counts and the click that follows it, so nothing but eight integers per click reaches the host.  Stops
+    once the IoU reaches ``max_iou_thr`` and at least ``min_clicks`` were made.  ``callback(image, gt_mask,
+    pred_mask, click_indx, clicks_list)`` runs after every prediction.  Returns ``(clicks_list, ious, mask)``:
+    the ``Click`` list, the IoU after every click (float32 array) and the last mask (bool (H, W), on the device).
+    ``max_clicks`` is at most 64, the clicked list that ``ops.next_click`` takes; more is refused before the
+    image is embedded."""
+    from .clicker import MAX_CLICKS, Clicker
+    assert 1 <= max_clicks <= MAX_CLICKS, f"evaluate_sample: max_clicks must be 1 .. {MAX_CLICKS}"
+    dev = predictor.device
+    clicker = Clicker(gt_mask=gt_mask, device=dev)
+    predictor.set_image(image)
+    size = tuple(clicker.gt_mask.shape)
+    pred = torch.zeros(size, dtype=torch.bool, device=dev)
+    nxt = clicker._get_next_click(pred)
+    low, ious = None, []
+    for click_indx in range(max_clicks):
+        clicker.add_click(nxt)
+        clicks = clicker.get_clicks()
+        xy = torch.tensor([[[c.coords[1], c.coords[0]] for c in clicks]], dtype=torch.float, device=dev)
+        labels = torch.tensor([[int(c.is_positive) for c in clicks]], dtype=torch.int, device=dev)
+        masks, _, low = predictor.predict_torch(predictor.transform.apply_coords_torch(xy, size), labels,
+                                                mask_input=low, multimask_output=False)
+        pred = masks[0, 0]
+        if callback is not None:
+            callback(image, gt_mask, pred, click_indx, clicker.clicks_list)
+        nxt = clicker._get_next_click(pred)        # this prediction's counts and the click after it
+        inter, union = clicker.last_counts
+        iou = inter / union if union else float("nan")
+        ious.append(iou)
+        if iou >= max_iou_thr and click_indx + 1 >= min_clicks:
+            break
+    return clicker.clicks_list, np.array(ious, dtype=np.float32), pred
+
+
+def compute_noc_metric(all_ious: Sequence[Sequence[float]], iou_thrs: Sequence[float], max_clicks: int = 20):
+    """Number of Clicks (reference ``inference/utils.py::compute_noc_metric``): per threshold the mean over the
+    samples of the 1-based index of the first click whose IoU reaches it (``max_clicks`` where none does), and
+    how many samples sit at ``max_clicks``.  Returns ``(noc_list, over_max_list)``."""
+    noc_list, over_max_list = [], []
+    for thr in iou_thrs:
+        scores = []
+        for ious in all_ious:
+            reached = np.flatnonzero(np.asarray(ious) >= thr)
+            scores.append(int(reached[0]) + 1 if len(reached) else max_clicks)
+        scores = np.array(scores, dtype=np.int64)
+        noc_list.append(scores.mean())
+        over_max_list.append(int((scores == max_clicks).sum()))
+    return noc_list, over_max_list

@@ -1230,3 +1230,38 @@ def rle_remove_small_regions(offsets: torch.Tensor, counts: torch.Tensor, size, 
     _lib.check(lib.samq_rle_regions_write(_ptr(offsets), n, total_in, hh, ww, _ptr(new_offsets), _ptr(ws), nws,
                                           _ptr(new_counts), total, _stream()), "rle_remove_small_regions")
     return new_offsets, new_counts, stats[:, :4], stats[:, 4], stats[:, 5] != 0
+
+
+# ----------------------------------------------------------------------------- click simulator
+def next_click(pred: torch.Tensor, gt: torch.Tensor, clicked: Optional[torch.Tensor] = None, ignore_label: int = -1,
+               dist: bool = False):
+    """The next click of the RITM protocol (``Clicker._get_next_click`` with padding) and the counts of ``get_iou``
+    per mask, in exact integers on the device (``samq_next_click``): the squared Euclidean distance transform of
+    the false-negative and the false-positive mask, each padded by a ring of zeros, and the first deepest pixel of
+    the larger error region.  ``pred`` bool / uint8 and ``gt`` int8 (1 object, 0 background, ``ignore_label``
+    neither), both (n, H, W) or (H, W), 1 <= H, W <= 4096; ``clicked`` int32 (n, K, 2) pixels ``(y, x)`` already
+    clicked (K <= 64; a slot with ``y < 0`` is unused).  Returns ``out`` int32 (n, 8) = ``[is_positive, y, x,
+    fn_max_d2, fp_max_d2, inter, union, 0]`` and, with ``dist=True``, also the two squared-distance maps int32
+    (n, 2, H, W) (clicked pixels not zeroed in them).  Nothing is read back to the host."""
+    _need_cuda(pred, gt, clicked)
+    assert pred.dim() in (2, 3) and pred.dtype in (torch.bool, torch.uint8), \
+        "next_click: pred must be bool / uint8 (n, H, W) or (H, W)"
+    assert gt.dtype == torch.int8 and gt.shape == pred.shape, "next_click: gt must be int8 of pred's shape"
+    h, w = int(pred.shape[-2]), int(pred.shape[-1])
+    pred, gt = pred.reshape(-1, h, w).contiguous(), gt.reshape(-1, h, w).contiguous()
+    n = pred.shape[0]
+    k = 0
+    if clicked is not None:
+        assert clicked.dtype == torch.int32 and clicked.dim() == 3 and clicked.shape[0] == n and clicked.shape[2] == 2, \
+            "next_click: clicked must be int32 (n, K, 2)"
+        k = int(clicked.shape[1])
+        clicked = clicked.contiguous() if k else None
+    lib = _lib.load()
+    # 0 for sizes the C entry rejects (it checks them before anything is launched): no map is allocated then
+    nws = lib.samq_next_click_workspace(n, h, w)
+    out = torch.empty((n, 8), dtype=torch.int32, device=pred.device)
+    ws = torch.empty(max((nws + 7) // 8, 1), dtype=torch.int64, device=pred.device)
+    d2 = torch.empty((n, 2, h, w), dtype=torch.int32, device=pred.device) if dist and (nws or n == 0) else None
+    _lib.check(lib.samq_next_click(_ptr(pred), _ptr(gt), _ptr(clicked), k, n, h, w, int(ignore_label), _ptr(out),
+                                   _ptr(d2), _ptr(ws), nws, _stream()), "next_click")
+    return (out, d2) if dist else out
