@@ -746,6 +746,34 @@ int samq_next_click(const uint8_t* pred, const int8_t* gt, const int32_t* clicke
                     int ignore_label, int32_t* out, int32_t* d2, void* workspace, size_t workspace_bytes,
                     hipStream_t stream);
 
+/* ---------------------------------------------------------------- image resize */
+
+/* ResizeLongestSide.apply_image (segment_anything/utils/transforms.py:26-32: PIL.Image.resize(.., BILINEAR)) of a
+ * window of a uint8 HWC image on the device, bit for bit, in one launch with no workspace and no host table.
+ *   img     uint8 (H, W, 3) contiguous; the window is rows y0 .. y1 - 1, columns x0 .. x1 - 1 (xyxy as
+ *           generate_crop_boxes gives it) and its edges clamp as an image's edges do: the result equals the
+ *           resize of the sliced array.
+ *   Per axis of window length n and output length m, in fp64 with every step its own IEEE operation:
+ *   scale = n / m, fs = max(scale, 1), center = (i + 0.5) scale, lo = max(0, (int)(center - fs + 0.5)),
+ *   hi = min(n, (int)(center + fs + 0.5)), w_t = max(0, 1 - |(t + lo - center + 0.5) / fs|), ww = sum w_t,
+ *   k_t = (int)(w_t / ww * 2^22 + 0.5), value = clamp(((1 << 21) + sum k_t pixel_t) >> 22, 0, 255).  The
+ *   horizontal pass runs first and writes uint8, the vertical pass reads it; an axis with n == m is skipped.
+ *   Equal to Pillow (12.2) for the sizes ResizeLongestSide.get_preprocess_shape gives, where both axes scale
+ *   alike; a strongly anisotropic resize (3000 x 8 to 64 x 2) was seen to differ by one code.
+ *   out     out_f32 == 0: uint8 planar (3, out_h, out_w), what SamPredictor.set_torch_image and
+ *           samq_patch_embed_u8 take.  out_f32 != 0: f32 planar (3, pad_to, pad_to) holding Sam.preprocess
+ *           (modeling/sam.py:164-174): (float(x) - pixel_mean[c]) / pixel_std[c] as an fp32 subtraction and a
+ *           correctly rounded division, 0 right of out_w and below out_h; pixel_mean / pixel_std f32 [3],
+ *           indexed by the OUTPUT channel.
+ *   flip    non-zero reverses the channel order on the way out (image_format != model.image_format).
+ * SAMQ_ERR_UNSUPPORTED: n > 16 m on an axis (a long side above 16384 at a target of 1024), an output side or
+ * pad_to above 16384.  SAMQ_ERR_INVALID: an empty output, an empty window or one outside the image, a null
+ * pointer, the float output without pixel_mean / pixel_std or with pad_to below the output size.  A null img
+ * with out_h == 0 or out_w == 0 is a no-op (SAMQ_OK).  All of these return before any device call. */
+int samq_resize_u8(const uint8_t* img, int H, int W, int x0, int y0, int x1, int y1, int out_h, int out_w, int flip,
+                   void* out, int out_f32, const float* pixel_mean, const float* pixel_std, int pad_to,
+                   hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,9 @@ SIGNATURES = {
     # click simulator: exact distance transform, next click, IoU counts
     "samq_next_click_workspace": (ctypes.c_size_t, [_i32, _i32, _i32]),
     "samq_next_click": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    # image resize in front of the encoder (PIL's antialiased bilinear, bit for bit)
+    "samq_resize_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32,
+                              _vp]),
 }
 
 

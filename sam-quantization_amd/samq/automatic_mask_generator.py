@@ -7,6 +7,8 @@ the defaults and the output records of ``segment_anything/automatic_mask_generat
 * per crop ``ops.box_nms`` on the predicted IoUs, across crops ``ops.box_nms`` on ``1 / crop area``;
 * with ``min_mask_region_area > 0`` ``ops.rle_remove_small_regions`` on the run lengths of the survivors (no mask is
   decoded) and a third ``ops.box_nms`` that prefers the masks it left untouched (``postprocess_small_regions``);
+* the image is uploaded once; every crop is resized from the resident copy (``SamPredictor.set_image`` with a
+  ``box``: ``ops.resize_u8`` on a window), not sliced, resized and uploaded again on the host;
 * host lists are built once per crop from the CSR tensors (one device-to-host copy per field), not once per mask.
 
 Host round trips, none of which grows with the number of masks.  Per batch: two reads (the size of the
@@ -141,6 +143,9 @@ class SamAutomaticMaskGenerator:
         NMS, and the (crop, row) pairs that survive the NMS across crops, in output order."""
         orig_size = tuple(image.shape[:2])
         crop_boxes, layers = generate_crop_boxes(orig_size, self.crop_n_layers, self.crop_overlap_ratio)
+        if self.predictor.device.type == "cuda":
+            # one upload; every crop is resized from the resident image (ops.resize_u8 on a window)
+            image = torch.as_tensor(np.ascontiguousarray(image), device=self.predictor.device)
         crops = [self._process_crop(image, box, layer, orig_size) for box, layer in zip(crop_boxes, layers)]
         crops = [c for c in crops if c is not None]
         where = [(ci, r) for ci, c in enumerate(crops) for r in range(len(c["boxes"]))]
@@ -203,9 +208,8 @@ class SamAutomaticMaskGenerator:
 
     def _process_crop(self, image, crop_box, layer, orig_size):
         x0, y0, x1, y1 = crop_box
-        crop = image[y0:y1, x0:x1, :]
-        crop_size = crop.shape[:2]
-        self.predictor.set_image(crop)
+        crop_size = (y1 - y0, x1 - x0)
+        self.predictor.set_image(image, box=crop_box)
         points = self.point_grids[layer] * np.array(crop_size)[None, ::-1]
         batches = []
         for b in range(0, len(points), self.points_per_batch):

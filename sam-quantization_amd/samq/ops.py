@@ -1265,3 +1265,37 @@ def next_click(pred: torch.Tensor, gt: torch.Tensor, clicked: Optional[torch.Ten
     _lib.check(lib.samq_next_click(_ptr(pred), _ptr(gt), _ptr(clicked), k, n, h, w, int(ignore_label), _ptr(out),
                                    _ptr(d2), _ptr(ws), nws, _stream()), "next_click")
     return (out, d2) if dist else out
+
+
+# ----------------------------------------------------------------------------- image resize
+def resize_u8(image: torch.Tensor, out_hw, box=None, flip: bool = False, norm=None, pad_to: Optional[int] = None):
+    """``PIL.Image.resize((w, h), BILINEAR)`` of a uint8 HWC image on the device, bit for bit (``samq_resize_u8``):
+    Pillow's antialiased triangle filter in two passes with 22-bit integer coefficients, in one launch with no
+    host table.  The contract is equality with Pillow for the sizes ``ResizeLongestSide.get_preprocess_shape``
+    gives (both axes scale alike up to rounding); a strongly anisotropic resize may differ by one code.
+    ``image`` CUDA uint8 (H, W, 3) contiguous; ``out_hw = (h, w)``; ``box = (x0, y0, x1, y1)`` (as
+    ``generate_crop_boxes``) resizes that window as if it were the sliced array; ``flip`` reverses the channel
+    order.  Returns uint8 planar (3, h, w), or with ``norm = (pixel_mean, pixel_std)`` and ``pad_to = P`` float32
+    (3, P, P) holding ``Sam.preprocess`` of it: ``(x - mean) / std`` in fp32, zero right of ``w`` and below ``h``.
+    A reduction above 16x on an axis raises ``NotImplementedError``."""
+    _need_cuda(image)
+    assert image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3 and image.is_contiguous(), \
+        "resize_u8: image must be a contiguous uint8 (H, W, 3) tensor"
+    assert (norm is None) == (pad_to is None), "resize_u8: norm and pad_to go together"
+    hh, ww = int(image.shape[0]), int(image.shape[1])
+    x0, y0, x1, y1 = (int(v) for v in box) if box is not None else (0, 0, ww, hh)
+    oh, ow = (int(v) for v in out_hw)
+    mean = std = None
+    p = 0
+    if norm is not None:
+        mean, std = (t.to(device=image.device, dtype=torch.float32).reshape(-1).contiguous() for t in norm)
+        assert mean.numel() == 3 and std.numel() == 3, "resize_u8: pixel_mean and pixel_std hold three values"
+        p = int(pad_to)
+    ok = 1 <= oh <= 16384 and 1 <= ow <= 16384 and (norm is None or max(oh, ow) <= p <= 16384)
+    # sizes the C entry rejects (it checks them before anything is launched) get no output buffer
+    shape = (0,) if not ok else (3, oh, ow) if norm is None else (3, p, p)
+    out = torch.empty(shape, dtype=torch.uint8 if norm is None else torch.float32, device=image.device)
+    _lib.check(_lib.load().samq_resize_u8(_ptr(image), hh, ww, x0, y0, x1, y1, oh, ow, int(bool(flip)),
+                                          _ptr(out), int(norm is not None), _ptr(mean), _ptr(std), p,
+                                          _stream()), "resize_u8")
+    return out

@@ -335,33 +335,71 @@ class SamPredictor:
         self.features = None
         self.orig_h = self.orig_w = self.input_h = self.input_w = None
 
-    def set_image(self, image: np.ndarray, image_format: str = "RGB") -> None:
+    def set_image(self, image, image_format: str = "RGB", box=None) -> None:
+        """Embed an HWC uint8 image: a numpy array, or a CUDA tensor that is already resident.  ``box = (x0, y0,
+        x1, y1)`` embeds that crop (``original_size`` becomes the crop's size).  With the model on a GPU the image
+        is uploaded once as it is and ``ops.resize_u8`` resizes it there, bit-equal to the PIL resize of
+        ``ResizeLongestSide.apply_image``; with the model on the CPU, or for a reduction the kernel refuses
+        (above 16x), the resize is the host's."""
         assert image_format in ("RGB", "BGR"), f"image_format must be in ['RGB', 'BGR'], is {image_format}."
-        if image_format != self.model.image_format:
+        flip = image_format != self.model.image_format
+        resident = isinstance(image, torch.Tensor)
+        x0, y0, x1, y1 = (int(v) for v in box) if box is not None else (0, 0, image.shape[1], image.shape[0])
+        size = (y1 - y0, x1 - x0)
+        if self.device.type == "cuda":
+            from . import ops
+            dev = image.contiguous() if resident else torch.as_tensor(np.ascontiguousarray(image), device=self.device)
+            hw = self.transform.get_preprocess_shape(*size, self.transform.target_length)
+            fused = self._fused_u8()
+            # an encoder without the uint8 entry gets Sam.preprocess from the same kernel
+            norm = {} if fused else {"norm": (self.model.pixel_mean, self.model.pixel_std),
+                                     "pad_to": self.model.image_encoder.img_size}
+            try:
+                t = ops.resize_u8(dev, hw, box, flip, **norm)[None]
+            except NotImplementedError:
+                t = None
+            if t is not None:
+                if fused:
+                    self.set_torch_image(t, size)
+                else:
+                    self._embed(t, hw, size, preprocessed=True)
+                return
+        if resident:
+            image = image.cpu().numpy()
+        image = image[y0:y1, x0:x1]
+        if flip:
             image = image[..., ::-1]
         inp = self.transform.apply_image(np.ascontiguousarray(image))
         t = torch.as_tensor(inp, device=self.device).permute(2, 0, 1).contiguous()[None]
         self.set_torch_image(t, image.shape[:2])
 
-    @torch.no_grad()
+    def _fused_u8(self) -> bool:
+        # only the GPTQ encoder (samq.modeling) has the uint8 patch-embedding entry; any other
+        # encoder (e.g. the fq_vit W8A8 one, which has no ``is_quantized``) takes preprocess + forward
+        fused_u8 = getattr(self.model.image_encoder, "is_quantized", None)
+        return fused_u8 is not None and bool(fused_u8())
+
     def set_torch_image(self, transformed_image: torch.Tensor, original_image_size) -> None:
         assert (transformed_image.dim() == 4 and transformed_image.shape[1] == 3
                 and max(*transformed_image.shape[2:]) == self.model.image_encoder.img_size), \
             f"set_torch_image input must be BCHW with long side {self.model.image_encoder.img_size}."
+        self._embed(transformed_image, transformed_image.shape[-2:], original_image_size)
+
+    @torch.no_grad()
+    def _embed(self, image: torch.Tensor, input_size, original_size, preprocessed: bool = False) -> None:
+        """Features of the resized pixels (1, 3, h, w) or, with ``preprocessed``, of what ``Sam.preprocess`` makes
+        of them (the float variant of ``ops.resize_u8``)."""
         self.reset_image()
-        self.original_size = tuple(original_image_size)
-        self.input_size = tuple(transformed_image.shape[-2:])
+        self.original_size = tuple(original_size)
+        self.input_size = tuple(input_size)
         enc = self.model.image_encoder
-        # only the GPTQ encoder (samq.modeling) has the uint8 patch-embedding entry; any other
-        # encoder (e.g. the fq_vit W8A8 one, which has no ``is_quantized``) takes preprocess + forward
-        fused_u8 = getattr(enc, "is_quantized", None)
-        if transformed_image.is_cuda and transformed_image.dtype == torch.uint8 and fused_u8 is not None and fused_u8():
+        if not preprocessed and image.is_cuda and image.dtype == torch.uint8 and self._fused_u8():
             # HIP engine: Sam.preprocess (normalise + zero-pad) runs inside the patch embedding
             # kernel on the raw uint8 pixels (samq_patch_embed_u8)
-            self.features = enc.engine()(transformed_image.contiguous(), out_dtype=torch.float32,
+            self.features = enc.engine()(image.contiguous(), out_dtype=torch.float32,
                                          pixel_norm=(self.model.pixel_mean, self.model.pixel_std))
         else:
-            x = self.model.preprocess(transformed_image.float())
+            x = image if preprocessed else self.model.preprocess(image.float())
             p = next(enc.parameters(), None)
             dt = p.dtype if p is not None and p.is_floating_point() else torch.float32
             self.features = enc(x.to(dt)).float()

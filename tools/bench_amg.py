@@ -19,6 +19,11 @@ Small regions (``--only regions``): ``ops.rle_remove_small_regions`` with ``min_
 192 blob masks at the three sizes, with the segments per mask, against the upstream host composition per mask
 (decode, connected components twice, box, re-encode) where the host has OpenCV or, failing that,
 ``scipy.ndimage``; the ``host`` field says which, ``null`` and no comparison if neither.
+
+Whole generator (``--only generate``): ``SamAutomaticMaskGenerator.generate`` with ``crop_n_layers=1`` (five crops,
+8 x 8 points each, no score filters) on a 1200 x 1800 image and a W4A16 vit_b with random weights: every crop
+resized from the resident image (``hip``) against ``set_image`` replaced by the host steps it took before
+``ops.resize_u8`` (``host``: slice, PIL resize, upload per crop), and whether the two give equal records.
 """
 import argparse
 import json
@@ -200,11 +205,38 @@ def regions_point(orig, reps, dev, min_area=100):
     return rec
 
 
+def generate_point(reps, dev, orig=(1200, 1800)):
+    import numpy as np
+    import samq
+    from samq.build_sam import Sam
+    from samq.synthetic import random_quant_encoder
+    torch.manual_seed(0)
+    gen = samq.SamAutomaticMaskGenerator(Sam(random_quant_encoder("vit_b", device=dev)).to(dev).eval(),
+                                         points_per_side=8, pred_iou_thresh=0.0, stability_score_thresh=0.0,
+                                         crop_n_layers=1, output_mode="uncompressed_rle")
+    image = np.random.Generator(np.random.PCG64(1)).integers(0, 256, orig + (3,), dtype=np.uint8)
+    pred, device_set_image = gen.predictor, gen.predictor.set_image
+
+    def host_set_image(_, image_format="RGB", box=None):
+        x0, y0, x1, y1 = box
+        crop = image[y0:y1, x0:x1]
+        inp = pred.transform.apply_image(np.ascontiguousarray(crop))
+        pred.set_torch_image(torch.as_tensor(inp, device=dev).permute(2, 0, 1).contiguous()[None], crop.shape[:2])
+
+    def run(set_image):
+        pred.set_image = set_image
+        return gen.generate(image)
+
+    res, out = compare({"host": lambda: run(host_set_image), "hip": lambda: run(device_set_image)}, reps)
+    return dict(op="generate", size=list(orig), crop_n_layers=1, records=len(out["hip"]), **res,
+                equal=out["hip"] == out["host"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default="")
-    ap.add_argument("--only", default="", choices=["", "mask_rle", "box_nms", "regions"])
+    ap.add_argument("--only", default="", choices=["", "mask_rle", "box_nms", "regions", "generate"])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_amg: no GPU visible; timings are taken on the GPU only")
@@ -213,8 +245,10 @@ def main():
     points = [lambda o=o, f=f: rle_point(o, f, a.reps, dev) for o in ((1024, 1024), (683, 1024), (1200, 1800))
               for f in (0.1, 0.5, 1.0)] + [lambda n=n: nms_point(n, a.reps, dev) for n in (192, 3072, 12288)]
     points += [lambda o=o: regions_point(o, a.reps, dev) for o in ((1024, 1024), (683, 1024), (1200, 1800))]
+    points += [lambda: generate_point(a.reps, dev)]
     if a.only:
-        points = [p for p, op in zip(points, ["mask_rle"] * 9 + ["box_nms"] * 3 + ["regions"] * 3) if op == a.only]
+        points = [p for p, op in zip(points, ["mask_rle"] * 9 + ["box_nms"] * 3 + ["regions"] * 3 + ["generate"])
+                  if op == a.only]
     for p in points:
         line = json.dumps(dict(p(), reps=a.reps, device=name))
         print(line, flush=True)
