@@ -591,6 +591,36 @@ int samq_upscale1_masks_q8(const int8_t* x, const void* w_hi, const void* w_lo, 
                            int B, int H, int W, int Cin, int Cout, int n_masks, float s_in, float s3, float s4,
                            float s_q1, hipStream_t stream);
 
+/* ---- the FLOAT mask decoder's tail (segment_anything/modeling/mask_decoder.py:126-144, everything
+ * behind the two-way transformer) on fp32 activations: two launches, no atomics, bit-identical from
+ * run to run.  Standard SAM shapes only: transformer width C == 256 (else SAMQ_ERR_UNSUPPORTED), four
+ * mask tokens, upscaling 256 -> 64 -> 32, three-layer MLPs of hidden width 256.  B == 0 (or an empty
+ * map): SAMQ_OK, nothing read.  16-byte aligned pointers. */
+
+/* The four hypernetwork MLPs and the IoU head (Linear-ReLU-Linear-ReLU-Linear, no sigmoid): MLP j < 4
+ * on token 1 + j of hs f32 [B, n_tokens, 256], MLP 4 (the IoU head) on token 0.  Weights TRANSPOSED,
+ * stacked over the five MLPs, the IoU head last: w1, w2 f32 [5][256 k][256 n], w3 f32 [5][256 k][32 n]
+ * (the IoU head's columns 4..31 zero), b1, b2 [5][256], b3 [5][32] (ops.mlp_pack_weight_f32).
+ * hyper f32 [B, 4, 32], iou f32 [B, 4].  One workgroup per (prompt, MLP); each output is one fp32 FMA
+ * chain over k in index order plus the bias.  n_tokens >= 5. */
+int samq_decoder_mlps_f32(const float* hs, const float* w1, const float* w2, const float* w3, const float* b1,
+                          const float* b2, const float* b3, float* hyper, float* iou, int B, int n_tokens, int C,
+                          hipStream_t stream);
+
+/* output_upscaling and the mask product fused per tile of 64 input pixels: keys f32 [B*h*w, 256] token
+ * rows (the transformer's second output) ->
+ *   m  = gelu_erf(LayerNorm2d_64(convT_k2s2(keys; w1) + b1; gamma, beta, eps))     (never stored)
+ *   u  = gelu_erf(convT_k2s2(m; w2) + b2)                                          (never stored)
+ *   masks f32 [B, 4, 4h, 4w] = sum_c hyper[b][m][c] u[b][c][Y][X]
+ * w1 / w2: the ConvTranspose2d weights [Cin, Cout, 2, 2] as W[n][k] = weight[k][co][kh][kw],
+ * n = (2 kh + kw) Cout + co, in fp32 MFMA fragment order [4 Cout / 32][Cin / 8][64 lanes][4], lane =
+ * 32 khalf + nn holds W[32 tile + nn][8 j + 4 khalf + 0..3] (ops.convt_frag_weight_f32).  Both GEMMs on
+ * v_mfma_f32_32x32x2_f32 (fp32 operands and accumulation); two-pass fp32 channel statistics.  hyper f32
+ * [B, 4, 32] (samq_decoder_mlps_f32's).  Tiles run over the flattened B*h*w index. */
+int samq_upscale_masks_f32(const float* keys, const float* w1, const float* b1, const float* gamma,
+                           const float* beta, const float* w2, const float* b2, const float* hyper, float* masks,
+                           int B, int h, int w, int C, float eps, hipStream_t stream);
+
 /* ---------------------------------------------------------------- patch embedding / neck */
 
 /* PatchEmbed (segment_anything/modeling/image_encoder.py:411-442) + pos_embed add (:108-110)

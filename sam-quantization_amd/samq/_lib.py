@@ -109,6 +109,10 @@ SIGNATURES = {
                                     _i32, _i32, _i32, _f32, _vp]),
     "samq_upscale1_masks_q8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                       _f32, _f32, _f32, _f32, _vp]),
+    # float mask decoder tail
+    "samq_decoder_mlps_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "samq_upscale_masks_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32,
+                                      _vp]),
     "samq_patch_embed": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "samq_patch_embed_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "samq_patch_embed_u8": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32,

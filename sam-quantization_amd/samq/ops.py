@@ -1102,6 +1102,76 @@ def upscale1_masks_q8(x: torch.Tensor, w_hi: torch.Tensor, w_lo: torch.Tensor, b
     return masks
 
 
+# ----------------------------------------------------------------------------- mask decoder tail (float)
+def convt_frag_weight_f32(weight: torch.Tensor) -> torch.Tensor:
+    """A ``ConvTranspose2d(k2 s2)`` fp32 weight [Cin, Cout, 2, 2] -> what ``samq_upscale_masks_f32`` reads:
+    the GEMM matrix W[n][k] = weight[k][co][kh][kw], n = (2 kh + kw) Cout + co, in fp32 MFMA fragment order
+    [4 Cout / 32][Cin / 8][64][4]: lane = 32 khalf + nn holds W[32 tile + nn][8 j + 4 khalf + 0..3]."""
+    cin, cout, kh, kw = weight.shape
+    assert (kh, kw) == (2, 2) and cin % 8 == 0 and (4 * cout) % 32 == 0
+    w = weight.detach().float().permute(2, 3, 1, 0).reshape(4 * cout, cin)
+    return w.reshape(4 * cout // 32, 32, cin // 8, 2, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(-1)
+
+
+def mlp_pack_weight_f32(weights, n_pad: int = 0) -> torch.Tensor:
+    """The fp32 weights [N, K] of one layer of several MLPs -> ``samq_decoder_mlps_f32``'s [n_mlp][K][max(N, n_pad)]
+    (transposed: a thread per output column reads coalesced; columns past N zero)."""
+    out = []
+    for w in weights:
+        w = w.detach().float()
+        if n_pad > w.shape[0]:
+            w = torch.cat([w, w.new_zeros((n_pad - w.shape[0], w.shape[1]))])
+        out.append(w.t())
+    return torch.stack(out).contiguous()
+
+
+def decoder_mlps_f32(hs: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, w3: torch.Tensor, b1: torch.Tensor,
+                     b2: torch.Tensor, b3: torch.Tensor, hyper: Optional[torch.Tensor] = None,
+                     iou: Optional[torch.Tensor] = None):
+    """``samq_decoder_mlps_f32``: hs (B, Nt, 256) f32, the transformer's tokens -> (hyper (B, 4, 32) f32,
+    iou_pred (B, 4) f32).  Weights from ``mlp_pack_weight_f32`` over the four hypernetwork MLPs and the IoU
+    head (last): w1, w2 (5, 256, 256), w3 (5, 256, 32), b1, b2 (5, 256), b3 (5, 32)."""
+    _need_cuda(hs, w1, w2, w3, b1, b2, b3, hyper, iou)
+    assert hs.dtype == torch.float32 and hs.dim() == 3 and hs.is_contiguous()
+    b, nt, c = hs.shape
+    for t, shp in ((w1, (5, c, 256)), (w2, (5, 256, 256)), (w3, (5, 256, 32)), (b1, (5, 256)), (b2, (5, 256)),
+                   (b3, (5, 32))):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shp, \
+            f"decoder_mlps_f32: expected a contiguous f32 {shp}, got {t.dtype} {tuple(t.shape)}"
+    if hyper is None:
+        hyper = torch.empty((b, 4, 32), dtype=torch.float32, device=hs.device)
+    if iou is None:
+        iou = torch.empty((b, 4), dtype=torch.float32, device=hs.device)
+    assert hyper.dtype == torch.float32 and hyper.is_contiguous() and tuple(hyper.shape) == (b, 4, 32)
+    assert iou.dtype == torch.float32 and iou.is_contiguous() and tuple(iou.shape) == (b, 4)
+    _lib.check(_lib.load().samq_decoder_mlps_f32(_ptr(hs), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(b1), _ptr(b2), _ptr(b3),
+                                                 _ptr(hyper), _ptr(iou), b, nt, c, _stream()), "decoder_mlps_f32")
+    return hyper, iou
+
+
+def upscale_masks_f32(keys: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                      eps: float, w2: torch.Tensor, b2: torch.Tensor, hyper: torch.Tensor, h: int, w: int,
+                      masks: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``samq_upscale_masks_f32``: keys (B, h*w, 256) f32 token rows, hyper (B, 4, 32) f32 -> masks
+    (B, 4, 4h, 4w) f32 = hyper @ GELU(convT(GELU(LayerNorm2d(convT(keys))))), the two upscaled maps never
+    stored.  w1 / w2 from ``convt_frag_weight_f32``."""
+    _need_cuda(keys, w1, b1, gamma, beta, w2, b2, hyper, masks)
+    assert keys.dtype == torch.float32 and keys.dim() == 3 and keys.is_contiguous()
+    b, hw, c = keys.shape
+    assert hw == h * w, "upscale_masks_f32: keys must be (B, h*w, C)"
+    for t, n in ((w1, 4 * 64 * c), (b1, 64), (gamma, 64), (beta, 64), (w2, 4 * 32 * 64), (b2, 32)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, \
+            f"upscale_masks_f32: expected {n} contiguous f32 values, got {t.dtype} {tuple(t.shape)}"
+    assert hyper.dtype == torch.float32 and hyper.is_contiguous() and tuple(hyper.shape) == (b, 4, 32)
+    if masks is None:
+        masks = torch.empty((b, 4, 4 * h, 4 * w), dtype=torch.float32, device=keys.device)
+    assert masks.dtype == torch.float32 and masks.is_contiguous() and tuple(masks.shape) == (b, 4, 4 * h, 4 * w)
+    _lib.check(_lib.load().samq_upscale_masks_f32(_ptr(keys), _ptr(w1), _ptr(b1), _ptr(gamma), _ptr(beta), _ptr(w2),
+                                                  _ptr(b2), _ptr(hyper), _ptr(masks), b, h, w, c, float(eps),
+                                                  _stream()), "upscale_masks_f32")
+    return masks
+
+
 # ----------------------------------------------------------------------------- mask post-processing
 def mask_postprocess(low: torch.Tensor, img_size: int, input_size, original_size, threshold: float = 0.0,
                      offset: float = 1.0, masks: bool = True):

@@ -228,6 +228,97 @@ class MaskDecoder(nn.Module):
         self.output_hypernetworks_mlps = nn.ModuleList(
             [MLP(transformer_dim, transformer_dim, c8, 3) for _ in range(self.num_mask_tokens)])
         self.iou_prediction_head = MLP(transformer_dim, iou_head_hidden_dim, self.num_mask_tokens, iou_head_depth)
+        # True: on CUDA fp32 inputs everything behind the transformer runs in two HIP launches
+        # (csrc/decoder_tail_f32.hip) instead of the module graph below.  Inference only: the kernels have
+        # no backward, so a call that autograd records (grad mode on and the transformer's outputs requiring
+        # grad, i.e. any call outside torch.no_grad() on a module with trainable parameters) keeps the module
+        # graph, as CPU tensors and non-fp32 dtypes do.  SamPredictor and the mask generator run under no_grad.
+        self.use_fused_tail = False
+        self._tail = None
+
+    # -- fused tail: packed weights, a snapshot of the tail's parameters
+    def refresh(self) -> None:
+        """Forget the packed tail weights; the next fused forward packs them again.  ``load_state_dict``,
+        ``.to()`` and in-place updates of the tail's parameters are noticed without it (the snapshot is keyed
+        by their storage addresses and version counters); call it after replacing a Parameter object by hand,
+        whose fresh tensor may land on a freed address with the same version."""
+        self._tail = None
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self.refresh()
+        super()._load_from_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        self.refresh()   # .to() / .cuda() / .half(): the snapshot lives on the old device
+        return super()._apply(fn, *args, **kwargs)
+
+    def _tail_params(self):
+        mods = (self.output_upscaling, self.output_hypernetworks_mlps, self.iou_prediction_head)
+        return [p for m in mods for p in m.parameters()]
+
+    def _check_tail_structure(self) -> None:
+        """The fused kernels are written for the standard SAM tail; anything else is refused by name."""
+        def bad(what):
+            raise NotImplementedError(f"MaskDecoder fused tail: {what}")
+
+        c = self.transformer_dim
+        if c != 256 or self.num_mask_tokens != 4:
+            bad(f"needs transformer_dim 256 and 4 mask tokens, found {c} and {self.num_mask_tokens}")
+        heads = [(f"output_hypernetworks_mlps[{i}]", m, c // 8) for i, m in enumerate(self.output_hypernetworks_mlps)]
+        for name, mlp, n_out in heads + [("iou_prediction_head", self.iou_prediction_head, self.num_mask_tokens)]:
+            dims = [(l.in_features, l.out_features) for l in mlp.layers]
+            if mlp.num_layers != 3 or dims != [(c, 256), (256, 256), (256, n_out)]:
+                bad(f"{name} must be 3 layers {c} -> 256 -> 256 -> {n_out}, found depth {mlp.num_layers} with "
+                    f"layers {dims}")
+            if mlp.sigmoid_output:
+                bad(f"{name} has sigmoid_output")
+        up = self.output_upscaling
+        kinds = [type(m).__name__ for m in up]
+        if not (len(up) == 5 and isinstance(up[0], nn.ConvTranspose2d) and isinstance(up[1], LayerNorm2d)
+                and isinstance(up[3], nn.ConvTranspose2d) and all(isinstance(up[i], nn.GELU) for i in (2, 4))):
+            bad(f"output_upscaling must be ConvTranspose2d, LayerNorm2d, GELU, ConvTranspose2d, GELU, found {kinds}")
+        for i in (2, 4):
+            if getattr(up[i], "approximate", "none") != "none":
+                bad(f"output_upscaling[{i}] must be the exact-erf GELU, found approximate='{up[i].approximate}'")
+        for i, cin, cout in ((0, c, c // 4), (3, c // 4, c // 8)):
+            m = up[i]
+            found = (m.in_channels, m.out_channels, tuple(m.kernel_size), tuple(m.stride), tuple(m.padding),
+                     tuple(m.output_padding), tuple(m.dilation), m.groups, m.bias is not None)
+            if found != (cin, cout, (2, 2), (2, 2), (0, 0), (0, 0), (1, 1), 1, True):
+                bad(f"output_upscaling[{i}] must be ConvTranspose2d({cin}, {cout}, kernel 2, stride 2) with a bias, "
+                    f"found {m}")
+
+    def _fused_tail(self):
+        params = self._tail_params()
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        t = self._tail
+        if t is not None and t["key"] == key:
+            return t
+        self._check_tail_structure()
+        from . import ops
+        up = self.output_upscaling
+        mlps = list(self.output_hypernetworks_mlps) + [self.iou_prediction_head]
+        f32 = lambda p: p.detach().float().contiguous()
+        layer = lambda i: [m.layers[i].weight for m in mlps]
+        bias = lambda i, n: torch.stack([F.pad(f32(m.layers[i].bias), (0, n - m.layers[i].out_features))
+                                         for m in mlps]).contiguous()
+        t = {"key": key,
+             "w1": ops.mlp_pack_weight_f32(layer(0)), "w2": ops.mlp_pack_weight_f32(layer(1)),
+             "w3": ops.mlp_pack_weight_f32(layer(2), n_pad=32),
+             "b1": bias(0, 256), "b2": bias(1, 256), "b3": bias(2, 32),
+             "u1": ops.convt_frag_weight_f32(up[0].weight), "ub1": f32(up[0].bias),
+             "gamma": f32(up[1].weight), "beta": f32(up[1].bias), "eps": float(up[1].eps),
+             "u2": ops.convt_frag_weight_f32(up[3].weight), "ub2": f32(up[3].bias)}
+        self._tail = t
+        return t
+
+    def _fused_tail_forward(self, hs, keys, h, w):
+        from . import ops
+        t = self._fused_tail()
+        hyper, iou = ops.decoder_mlps_f32(hs.contiguous(), t["w1"], t["w2"], t["w3"], t["b1"], t["b2"], t["b3"])
+        masks = ops.upscale_masks_f32(keys.contiguous(), t["u1"], t["ub1"], t["gamma"], t["beta"], t["eps"], t["u2"],
+                                      t["ub2"], hyper, h, w)
+        return masks, iou
 
     def predict_masks(self, image_embeddings, image_pe, sparse_prompt_embeddings, dense_prompt_embeddings):
         dt = image_embeddings.dtype
@@ -239,6 +330,9 @@ class MaskDecoder(nn.Module):
         pos = image_pe.repeat_interleave(n, dim=0)
         b, c, h, w = src.shape
         hs, src = self.transformer(src, pos, tokens)
+        if (self.use_fused_tail and hs.is_cuda and hs.dtype == torch.float32 and src.dtype == torch.float32
+                and not (torch.is_grad_enabled() and (hs.requires_grad or src.requires_grad))):
+            return self._fused_tail_forward(hs, src, h, w)   # inference only: the kernels have no backward
         up = self.output_upscaling(src.transpose(1, 2).reshape(b, c, h, w))
         hyper = torch.stack([mlp(hs[:, 1 + i]) for i, mlp in enumerate(self.output_hypernetworks_mlps)], dim=1)
         bu, cu, hu, wu = up.shape

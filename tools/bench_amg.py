@@ -24,6 +24,8 @@ Whole generator (``--only generate``): ``SamAutomaticMaskGenerator.generate`` wi
 8 x 8 points each, no score filters) on a 1200 x 1800 image and a W4A16 vit_b with random weights: every crop
 resized from the resident image (``hip``) against ``set_image`` replaced by the host steps it took before
 ``ops.resize_u8`` (``host``: slice, PIL resize, upload per crop), and whether the two give equal records.
+``--fused-tail on`` runs it with the float mask decoder's fused tail; ``--only generate_tail`` alternates the same
+``generate`` with the tail as the module graph (``module``) and as the two HIP launches (``hip``).
 """
 import argparse
 import json
@@ -205,7 +207,7 @@ def regions_point(orig, reps, dev, min_area=100):
     return rec
 
 
-def generate_point(reps, dev, orig=(1200, 1800)):
+def generate_point(reps, dev, orig=(1200, 1800), fused_tail=False):
     import numpy as np
     import samq
     from samq.build_sam import Sam
@@ -214,6 +216,7 @@ def generate_point(reps, dev, orig=(1200, 1800)):
     gen = samq.SamAutomaticMaskGenerator(Sam(random_quant_encoder("vit_b", device=dev)).to(dev).eval(),
                                          points_per_side=8, pred_iou_thresh=0.0, stability_score_thresh=0.0,
                                          crop_n_layers=1, output_mode="uncompressed_rle")
+    gen.predictor.model.mask_decoder.use_fused_tail = fused_tail
     image = np.random.Generator(np.random.PCG64(1)).integers(0, 256, orig + (3,), dtype=np.uint8)
     pred, device_set_image = gen.predictor, gen.predictor.set_image
 
@@ -228,15 +231,39 @@ def generate_point(reps, dev, orig=(1200, 1800)):
         return gen.generate(image)
 
     res, out = compare({"host": lambda: run(host_set_image), "hip": lambda: run(device_set_image)}, reps)
-    return dict(op="generate", size=list(orig), crop_n_layers=1, records=len(out["hip"]), **res,
+    return dict(op="generate", size=list(orig), crop_n_layers=1, fused_tail=fused_tail, records=len(out["hip"]), **res,
                 equal=out["hip"] == out["host"])
+
+
+def generate_tail_point(reps, dev, orig=(1200, 1800)):
+    """One ``generate`` of the float decoder behind the GPTQ encoder, the decoder's tail as the module graph
+    (``module``) against the two fused launches (``hip``: ``mask_decoder.use_fused_tail = True``), alternating."""
+    import numpy as np
+    import samq
+    from samq.build_sam import Sam
+    from samq.synthetic import random_quant_encoder
+    torch.manual_seed(0)
+    gen = samq.SamAutomaticMaskGenerator(Sam(random_quant_encoder("vit_b", device=dev)).to(dev).eval(),
+                                         points_per_side=8, pred_iou_thresh=0.0, stability_score_thresh=0.0,
+                                         crop_n_layers=1, output_mode="uncompressed_rle")
+    image = np.random.Generator(np.random.PCG64(1)).integers(0, 256, orig + (3,), dtype=np.uint8)
+
+    def run(fused):
+        gen.predictor.model.mask_decoder.use_fused_tail = fused
+        return gen.generate(image)
+
+    res, out = compare({"module": lambda: run(False), "hip": lambda: run(True)}, reps)
+    return dict(op="generate_tail", size=list(orig), crop_n_layers=1, records=len(out["hip"]),
+                records_module=len(out["module"]), **res)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default="")
-    ap.add_argument("--only", default="", choices=["", "mask_rle", "box_nms", "regions", "generate"])
+    ap.add_argument("--only", default="", choices=["", "mask_rle", "box_nms", "regions", "generate", "generate_tail"])
+    ap.add_argument("--fused-tail", choices=["off", "on"], default="off",
+                    help="the float mask decoder's tail in the other points: module graph (off) or the two HIP launches")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_amg: no GPU visible; timings are taken on the GPU only")
@@ -245,10 +272,11 @@ def main():
     points = [lambda o=o, f=f: rle_point(o, f, a.reps, dev) for o in ((1024, 1024), (683, 1024), (1200, 1800))
               for f in (0.1, 0.5, 1.0)] + [lambda n=n: nms_point(n, a.reps, dev) for n in (192, 3072, 12288)]
     points += [lambda o=o: regions_point(o, a.reps, dev) for o in ((1024, 1024), (683, 1024), (1200, 1800))]
-    points += [lambda: generate_point(a.reps, dev)]
+    points += [lambda: generate_point(a.reps, dev, fused_tail=a.fused_tail == "on"),
+               lambda: generate_tail_point(a.reps, dev)]
     if a.only:
-        points = [p for p, op in zip(points, ["mask_rle"] * 9 + ["box_nms"] * 3 + ["regions"] * 3 + ["generate"])
-                  if op == a.only]
+        ops_ = ["mask_rle"] * 9 + ["box_nms"] * 3 + ["regions"] * 3 + ["generate", "generate_tail"]
+        points = [p for p, op in zip(points, ops_) if op == a.only]
     for p in points:
         line = json.dumps(dict(p(), reps=a.reps, device=name))
         print(line, flush=True)

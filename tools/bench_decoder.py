@@ -17,6 +17,10 @@ Four paths on the same calibrated model (default initialisation, minmax calibrat
 Also counted (torch profiler): the launches of one click on each path, and in ``launch_split`` those of
 the prompt encoder, of one transformer forward, of the module-graph tail (upscaling, hypernetwork
 MLPs, IoU head) and of the fused tail.  One JSON line per path.
+
+    python tools/bench_decoder.py --float-tail both [--prompts 64] [--rounds 5]
+
+times the FLOAT model's decoder call instead (see ``float_main``).
 """
 import argparse
 import json
@@ -80,13 +84,90 @@ def launches(fn):
         return None
 
 
+def float_main(args):
+    """The FLOAT model's decoder call (prompt encoder + ``sam_decoder.MaskDecoder``) with ``--prompts`` one-point
+    prompts, its tail as the module graph (``tail_off``) or the two fused launches (``tail_on``:
+    ``use_fused_tail = True``).  With ``both`` the two alternate in rounds of ``--clicks`` calls, ``--rounds`` times;
+    then the same for the tail alone on random ``hs`` / ``keys``.  One JSON line per path: the median over the rounds
+    of each round's median, the spread of those medians, for the call and for the tail alone, and the launches of
+    one call and of the tail alone."""
+    from samq.sam_decoder import build_prompt_decoder
+    torch.manual_seed(0)
+    img = args.grid * 16
+    pe, md = build_prompt_decoder(image_size=img)
+    pe, md = pe.cuda().eval(), md.cuda().eval()
+    g = torch.Generator(device="cpu").manual_seed(1)
+    emb = torch.randn((1, 256, args.grid, args.grid), generator=g).cuda()
+    pts = ((torch.rand((args.prompts, 1, 2), generator=g) * img).cuda(),
+           torch.ones((args.prompts, 1), dtype=torch.int32).cuda())
+    dense_pe = pe.get_dense_pe()
+
+    @torch.no_grad()
+    def call(fused):
+        md.use_fused_tail = fused
+        sparse, dense = pe(points=pts, boxes=None, masks=None)
+        return md(emb, dense_pe, sparse, dense, True)
+
+    hs = torch.randn((args.prompts, 7, 256), device="cuda")
+    keys = torch.randn((args.prompts, args.grid * args.grid, 256), device="cuda")
+
+    @torch.no_grad()
+    def tail(fused):
+        if fused:
+            return md._fused_tail_forward(hs, keys, args.grid, args.grid)
+        up = md.output_upscaling(keys.transpose(1, 2).reshape(args.prompts, 256, args.grid, args.grid))
+        hyper = torch.stack([m(hs[:, 1 + i]) for i, m in enumerate(md.output_hypernetworks_mlps)], dim=1)
+        return (hyper @ up.flatten(2)), md.iou_prediction_head(hs[:, 0])
+
+    paths = {"off": ["tail_off"], "on": ["tail_on"], "both": ["tail_off", "tail_on"]}[args.float_tail]
+
+    def rounds(fn):
+        """Sorted round medians (ms) per path: warm-up of each, then the paths alternate round by round."""
+        meds = {p: [] for p in paths}
+        for p in paths:
+            for _ in range(args.warmup):
+                fn(p == "tail_on")
+        for _ in range(args.rounds):
+            for p in paths:
+                times = []
+                for _ in range(args.clicks):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn(p == "tail_on")
+                    torch.cuda.synchronize()
+                    times.append(time.perf_counter() - t0)
+                meds[p].append(1e3 * sorted(times)[len(times) // 2])
+        return {p: sorted(m) for p, m in meds.items()}
+
+    whole, alone = rounds(call), rounds(tail)
+    for p in paths:
+        fused = p == "tail_on"
+        m, t = whole[p], alone[p]
+        rec = dict(path=p, model="float", grid=args.grid, prompts=args.prompts, clicks=args.clicks,
+                   rounds=args.rounds, device=torch.cuda.get_device_name(0), ms_median=m[len(m) // 2],
+                   ms_round_min=m[0], ms_round_max=m[-1], tail_only_ms_median=t[len(t) // 2],
+                   tail_only_ms_round_min=t[0], tail_only_ms_round_max=t[-1],
+                   launches_per_call=launches(lambda: call(fused)), launches_tail=launches(lambda: tail(fused)))
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=64)
     ap.add_argument("--clicks", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--float-tail", choices=["off", "on", "both"], default=None,
+                    help="time the FLOAT model's decoder call instead, its tail as modules, fused, or alternating")
+    ap.add_argument("--prompts", type=int, default=1, help="prompts per call of the float model")
+    ap.add_argument("--rounds", type=int, default=5, help="alternating rounds of the float model's paths")
     args = ap.parse_args()
+    if args.float_tail is not None:
+        return float_main(args)
     pe, md, (emb, pts) = build(args.grid)
     eng = md.engine()
     dense_pe = pe.get_dense_pe()
